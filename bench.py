@@ -1,6 +1,6 @@
 """Benchmark of the MI355X segment query hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c1|c4|c6|c7]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c1|c4|c6|c7] [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 The default workload is c5, BASELINE configs[4] -- the metric's own shape: bitmap inverted-index AND/OR filter +
@@ -8,6 +8,11 @@ group-by SUM over 4096 x 2M-row segments, sharded over the GPUs.  A "step" is on
 this rank's segments resident in HBM: predicate values resolved to dictId space for every segment (a-4, in the
 library), bitmap sub-tree expansion, filter + decode + aggregate in the fused HIP kernel, the on-device combine, the
 result back to the host, and for N>1 the cross-GPU merge.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (throughput, ms_per_step, the result's summary).
+--dump-outputs DIR also writes what the last timed step returned as DIR/<name>.npy (float64; the data is seeded, so two
+builds compare output for output).  --full adds the measurements that take runs of their own: the one-query-at-a-time
+latency, the kernel timing window and roofline of the step, the PMC traffic on file and the CPU baseline.
 """
 import argparse
 import json
@@ -47,7 +52,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=os.environ.get("PGX_WORKLOAD", "c5"))
     ap.add_argument("--rows", type=int, default=0, help="override rows per segment (smoke/debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the lone-query latency, the step's kernel time and roofline, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--profile-iters", type=int, default=0, help="only run K steps (for rocprofv3 PMC passes)")
     ap.add_argument("--no-partition", action="store_true",
                     help="sparse group-by through the global hash table (PGX_X_NO_PARTITION), not the partitioned path")
@@ -213,6 +222,77 @@ def cpu_baseline_c4(data, req):
                       "%d selected docs summed by oracle/pinot_oracle.py on one thread, best of 3 after 1 warm-up; "
                       "%.3f ms per query" % (sd.total_raw_docs, sd.total_docs, len(docs), best * 1e3),
             "docs_scanned": int(len(docs))}
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together stay under this
+
+
+def _key_number(part):
+    """A group-key part as a float64: numeric keys as their value, string keys as the CRC-32 of their UTF-8 bytes."""
+    import zlib
+    try:
+        return float(part)
+    except ValueError:
+        return float(zlib.crc32(part.encode()))
+
+
+def _map_arrays(ncols, m):
+    """One trimmed {string key: value} map as (keys float64 [n, ncols], values float64 [n, 2]: value, count), rows
+    sorted by key so that the order does not depend on how ties fell in the trim."""
+    import numpy as np
+    keys = np.array([[_key_number(p) for p in k.split("\t")] for k in m], dtype=np.float64).reshape(len(m), ncols)
+    vals = np.array([(v[0], v[1]) if isinstance(v, tuple) else (v, 0) for v in m.values()],
+                    dtype=np.float64).reshape(len(m), 2)
+    order = np.lexsort(keys.T[::-1]) if len(m) else np.zeros(0, dtype=np.int64)
+    return keys[order], vals[order]
+
+
+def dump_outputs(outdir, E, q, req, last, segs, st, merged):
+    """--dump-outputs: the result of the last timed step, as a caller of the step receives it, in float64 .npy files.
+
+    stats.npy                      the execution statistics of the result (pgx_result_stats)
+    aggregation.npy                aggregation-only queries: [functions, 2] = (value, count)
+    top_keys_<i>, top_values_<i>   group-by: the trimmed combine output of function i (E.trimmed_maps; over all GPUs
+                                   the merged maps): keys [n, group columns], values [n, 2] = (value, count), by key
+    group_keys, group_values,      1 GPU: every group of the result (E.group_partials), sorted by key:
+    group_counts                   keys [group columns, n], values and counts [functions, n]; when that is more than
+                                   the size limit, the groups a fixed hash of the key selects
+    """
+    import numpy as np
+    from pinot_amd import synth
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "stats.npy"), np.array(list(st), dtype=np.float64))
+    if not req.get("group_by"):
+        if merged is not None:
+            res = merged
+        else:
+            res = E.decode_result(q, last, segs).get_aggregation_result()
+        rows = [(v[0], v[1]) if isinstance(v, tuple) else (v, 0) for v in res]
+        np.save(os.path.join(outdir, "aggregation.npy"), np.array(rows, dtype=np.float64).reshape(len(rows), 2))
+        return
+    ncols = len(q.group_cols)
+    maps = merged if merged is not None else E.trimmed_maps(q, last, segs)
+    for i, m in enumerate(maps):
+        keys, vals = _map_arrays(ncols, m)
+        np.save(os.path.join(outdir, "top_keys_%d.npy" % i), keys)
+        np.save(os.path.join(outdir, "top_values_%d.npy" % i), vals)
+    if merged is not None:
+        return
+    cols, vals, cnts = E.group_partials(q, last, segs)
+    keys = np.array([[_key_number(x) for x in c] if c.dtype.kind in "US" else c.astype(np.float64) for c in cols],
+                    dtype=np.float64).reshape(ncols, vals.shape[1])
+    nbytes = 8 * (keys.shape[0] + 2 * vals.shape[0]) * keys.shape[1]
+    budget = DUMP_LIMIT_BYTES - (1 << 20)  # the small files above and the .npy headers
+    if nbytes > budget:  # a fixed sample: the groups whose key hashes under the kept fraction
+        h = np.zeros(keys.shape[1], dtype=np.uint64)
+        for k in keys:
+            h = synth.splitmix64_np(h ^ k.view(np.uint64))
+        keep = (h >> np.uint64(11)).astype(np.float64) < 0.9 * budget / nbytes * float(1 << 53)
+        keys, vals, cnts = keys[:, keep], vals[:, keep], cnts[:, keep]
+    order = np.lexsort(keys[::-1])
+    np.save(os.path.join(outdir, "group_keys.npy"), keys[:, order])
+    np.save(os.path.join(outdir, "group_values.npy"), vals[:, order].astype(np.float64))
+    np.save(os.path.join(outdir, "group_counts.npy"), cnts[:, order].astype(np.float64))
 
 
 def main():
@@ -383,7 +463,7 @@ def main():
     # latency-bound workloads (C1, C4) take more samples
     t_lat = []
     n_lat = 15 if args.workload in ("c1", "c4") else 3
-    for k in range(2 + n_lat):
+    for k in range(2 + n_lat if args.full else 0):
         t1 = time.perf_counter()
         L.pgx_result_release(step())
         if k >= 2:
@@ -407,7 +487,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
 
-    # result summary (for the log) and kernel roofline on rank 0
+    # result summary (for the log) and, with --dump-outputs, the result itself on rank 0
     st = (C.c_int64 * 4)()
     N.check(L.pgx_result_stats(last, st))
     summary = None
@@ -422,6 +502,8 @@ def main():
             summary = {"groups": ngroups, "top3_" + q.fns[0]: best}
         else:
             summary = E.decode_result(q, last, segs).get_aggregation_result()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, E, q, req, last, segs, st, merged[0])
     L.pgx_result_release(last)
     total_rows = rows * (wl.segments * world if wl.scaling == "weak" else wl.segments)
     value = total_rows / (elapsed / args.steps)
@@ -432,13 +514,37 @@ def main():
     timing_steps = 5
     tout = (C.c_double * 3)()
     tjson = C.create_string_buffer(8192)
-    N.check(L.pgx_timing_start(ctx.handle))
-    run_steps(timing_steps)
-    N.check(L.pgx_timing_stop(ctx.handle, tout, tjson, len(tjson)))
-    step_kernels = json.loads(tjson.value.decode())
-    kernel_ms = tout[0] / timing_steps
+    if args.full:
+        N.check(L.pgx_timing_start(ctx.handle))
+        run_steps(timing_steps)
+        N.check(L.pgx_timing_stop(ctx.handle, tout, tjson, len(tjson)))
     if rank != 0:
         return
+    ms_step = 1e3 * elapsed / args.steps
+    if merged[0] is not None and req.get("group_by"):
+        top = merged[0][0]
+        best = sorted(top.items(), key=lambda kv: kv[1], reverse=q.fns[0] != "min")[:3]
+        summary = {"local": summary, "merged_over_gpus": {"top3_" + q.fns[0]: best}}
+    elif merged[0] is not None:
+        summary = {"local": summary, "merged_over_gpus": merged[0]}
+    line = {
+        "metric": METRIC, "value": value, "unit": "rows/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
+        "queries_in_flight": inflight,
+        "scaling": wl.scaling, "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic: device-generated v1 fixed-bit segments (seed %d), dictionaries per SURVEY 8d" % wl.seed,
+        "config": {"workload": wl.name + ": " + wl.description, "query": wl.query,
+                   "rows_per_segment": rows, "segments": len(segs) * (world if wl.scaling == "weak" else 1),
+                   "rows_total": total_rows, "parallelism": "dp%d (segment sharding)" % world,
+                   **({"exec": "PGX_X_NO_PARTITION (global hash table)"} if args.no_partition else {})},
+        "result": summary, "stats": list(st), "gen_s": t_gen,
+    }
+    if not args.full:  # a plain run: the headline figure only
+        print(json.dumps(line))
+        data.free()
+        return
+    step_kernels = json.loads(tjson.value.decode())
+    kernel_ms = tout[0] / timing_steps
     # forward-index bytes of every column the kernel decodes, serialized roaring bytes of every bitmap a
     # bitmap-index leaf ORs (inverted columns, non-RANGE predicates: FilterPlanNode.java:118-132), dictionaries.
     bitmap_leaves = [(lf, np.nonzero(E.leaf_matching_ids(segs[0].column(lf["column"]), lf))[0])
@@ -458,7 +564,6 @@ def main():
     # interpreter kernel), bitmap programs, partition / aggregation / trim kernels -- busy union per step
     kernel_name = "all kernels of the step (busy union): " + ", ".join(
         "%s x%d" % (k, v[0] // timing_steps) for k, v in sorted(step_kernels["kernels"].items()))
-    ms_step = 1e3 * elapsed / args.steps
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
     traffic = None
     tf = os.path.join(ROOT, "profiles", "traffic_%s.json" % wl.name)
@@ -476,23 +581,8 @@ def main():
         cpu = cpu_baseline_c1(data)
     elif world == 1 and not args.no_cpu_baseline and wl.name == "c4":
         cpu = cpu_baseline_c4(data, req)
-    if merged[0] is not None and req.get("group_by"):
-        top = merged[0][0]
-        best = sorted(top.items(), key=lambda kv: kv[1], reverse=q.fns[0] != "min")[:3]
-        summary = {"local": summary, "merged_over_gpus": {"top3_" + q.fns[0]: best}}
-    elif merged[0] is not None:
-        summary = {"local": summary, "merged_over_gpus": merged[0]}
-    line = {
-        "metric": METRIC, "value": value, "unit": "rows/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "queries_in_flight": inflight, "single_query_ms": 1e3 * min(t_lat),
-        "single_query_ms_median": 1e3 * sorted(t_lat)[len(t_lat) // 2],
-        "scaling": wl.scaling, "vs_baseline": None, "dtype": "int64",
-        "data": "synthetic: device-generated v1 fixed-bit segments (seed %d), dictionaries per SURVEY 8d" % wl.seed,
-        "config": {"workload": wl.name + ": " + wl.description, "query": wl.query,
-                   "rows_per_segment": rows, "segments": len(segs) * (world if wl.scaling == "weak" else 1),
-                   "rows_total": total_rows, "parallelism": "dp%d (segment sharding)" % world,
-                   **({"exec": "PGX_X_NO_PARTITION (global hash table)"} if args.no_partition else {})},
+    line.update({
+        "single_query_ms": 1e3 * min(t_lat), "single_query_ms_median": 1e3 * sorted(t_lat)[len(t_lat) // 2],
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "kernel": kernel_name, "kernel_ms": kernel_ms, "algorithmic_bytes": algo_bytes,
@@ -504,8 +594,7 @@ def main():
                      "kernels_per_step": {k: [v[0] / timing_steps, v[1] / timing_steps]
                                           for k, v in step_kernels["kernels"].items()}},
         "cpu_baseline": cpu,
-        "result": summary, "stats": list(st), "gen_s": t_gen,
-    }
+    })
     print(json.dumps(line))
     data.free()
 

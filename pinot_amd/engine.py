@@ -207,8 +207,10 @@ class IndexSegment:
         return self
 
     @classmethod
-    def from_device(cls, ctx: Context, seg: SegmentData, fwd_device: Dict[str, int]):
-        """Stage a segment whose forward indexes already live in HBM (synthetic benchmark data)."""
+    def from_device(cls, ctx: Context, seg: SegmentData, fwd_device: Dict[str, int], dict_device=None):
+        """Stage a segment whose forward indexes already live in HBM (synthetic benchmark data).  `dict_device`:
+        column name -> device copy of that column's dictionary bytes, kept by a caller that stages many segments
+        with the same dictionary; the other columns' dictionaries are copied to the device for the staging."""
         self = cls.__new__(cls)
         self.uid = next(_SEG_UID)
         self.ctx = ctx
@@ -230,17 +232,19 @@ class IndexSegment:
             d.dict_width = c.dict_width
             d.fwd = C.c_void_p(fwd_device[name][0])
             d.fwd_len = fwd_device[name][1]
-            p = C.c_void_p()
-            N.check(N.lib().pgx_device_alloc(ctx.handle, len(c.dict_bytes), C.byref(p)))
-            N.check(N.lib().pgx_copy_to_device(ctx.handle, p, c.dict_bytes, len(c.dict_bytes)))
-            dict_dev.append(p)
+            p = (dict_device or {}).get(name)
+            if p is None:
+                p = C.c_void_p()
+                N.check(N.lib().pgx_device_alloc(ctx.handle, len(c.dict_bytes), C.byref(p)))
+                N.check(N.lib().pgx_copy_to_device(ctx.handle, p, c.dict_bytes, len(c.dict_bytes)))
+                dict_dev.append(p)
             d.dict = p
             d.dict_len = len(c.dict_bytes)
             if c.inv_bytes is not None:  # inverted index bytes are host memory in either mode (pgx.h)
-                ib = C.create_string_buffer(bytes(c.inv_bytes), len(c.inv_bytes))
+                ib = c.inv_bytes if isinstance(c.inv_bytes, bytes) else bytes(c.inv_bytes)
                 keep.append(ib)
-                d.inv = C.cast(ib, C.c_void_p)
-                d.inv_len = len(c.inv_bytes)
+                d.inv = C.cast(C.c_char_p(ib), C.c_void_p)  # the bytes object's own buffer: staging only reads it
+                d.inv_len = len(ib)
         sd = N.SegmentDesc()
         sd.name = seg.name.encode()
         sd.total_docs = seg.total_docs

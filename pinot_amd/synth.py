@@ -251,19 +251,35 @@ class DeviceSegments:
         self.wl = wl
         self.rows = rows or wl.rows
         self.seg_ids = list(seg_ids)
-        self.buffers = []
+        self.buffers = []  # one pointer per (segment, column) forward index
+        self.allocs = []   # the device allocations behind them: one per segment
         self.segments = []
         self.inv_offsets = {}
         L = N.lib()
-        inv = self._inverted_indexes()
+        inv = self._inverted_indexes()  # futures: the host threads build them while this loop generates and stages
+        # dictionaries that do not depend on the segment: their bytes made once, one device copy for every staging
+        shared_bytes = {}
+        shared_dev = {}
+        for c in wl.columns:
+            if c.dict_kind not in ("metric_seg", "metric_f64_seg"):
+                b = make_dictionary(c.dict_kind, c.card).astype(">i4").tobytes()
+                p = C.c_void_p()
+                N.check(L.pgx_device_alloc(ctx.handle, len(b), C.byref(p)))
+                N.check(L.pgx_copy_to_device(ctx.handle, p, b, len(b)))
+                shared_bytes[c.name], shared_dev[c.name] = b, p
         for s in self.seg_ids:
-            dicts = {c.name: make_dictionary(c.dict_kind, c.card, s) for c in wl.columns}
             cols = []
             fwd_dev = {}
+            # the segment's forward indexes in one allocation (padded_fwd_bytes is a multiple of 64: each stays aligned)
+            sizes = [padded_fwd_bytes(self.rows, c.bits) for c in wl.columns]
+            base = C.c_void_p()
+            N.check(L.pgx_device_alloc(ctx.handle, sum(sizes), C.byref(base)))
+            self.allocs.append(base)
+            at = base.value
             for ci, c in enumerate(wl.columns):
-                nbytes = padded_fwd_bytes(self.rows, c.bits)
-                p = C.c_void_p()
-                N.check(L.pgx_device_alloc(ctx.handle, nbytes, C.byref(p)))
+                nbytes = sizes[ci]
+                p = C.c_void_p(at)
+                at += nbytes
                 self.buffers.append(p)
                 if c.paired:  # the pair -> value map is global; the row -> pair draw is per segment
                     N.check(L.pgx_synth_column_paired(ctx.handle, p, self.rows, c.bits, c.card,
@@ -274,19 +290,27 @@ class DeviceSegments:
                                                column_seed(wl.seed, s, ci)))
                 fwd_dev[c.name] = (p.value, nbytes)
                 f64 = c.dict_kind == "metric_f64_seg"
-                dict_bytes = dicts[c.name].astype(">f8" if f64 else ">i4").tobytes()
+                dict_bytes = shared_bytes.get(c.name)
+                if dict_bytes is None:
+                    dict_bytes = make_dictionary(c.dict_kind, c.card, s).astype(">f8" if f64 else ">i4").tobytes()
                 inv_bytes = inv.pop((s, ci), None)
                 if inv_bytes is not None:
+                    inv_bytes = inv_bytes.result()
                     self.inv_offsets[(s, c.name)] = np.frombuffer(inv_bytes, dtype=">u4", count=c.card + 1).astype(
                         np.int64)
                 cols.append(Column(c.name, "DOUBLE" if f64 else "INT", "DIMENSION", c.card, c.bits, self.rows, self.rows,
                                    False, inv_bytes is not None, dict_bytes, 8 if f64 else 4, None, None, inv_bytes))
             seg = SegmentData("%s_%d" % (wl.name, s), self.rows, self.rows, {c.name: c for c in cols})
-            self.segments.append(IndexSegment.from_device(ctx, seg, fwd_dev))
+            self.segments.append(IndexSegment.from_device(ctx, seg, fwd_dev, shared_dev))
+            for col in cols:  # staging copied the index; inv_offsets keeps what algorithmic_bytes reads of it
+                col.inv_bytes = None
+        for p in shared_dev.values():  # staging copied them
+            L.pgx_device_free(ctx.handle, p)
 
     def _inverted_indexes(self):
         """Roaring inverted indexes of the workload's inverted columns, built on host threads from the same dictIds
-        the device generator packs (pgx_synth_dict_ids + pgx_inverted_index_build, both release the GIL)."""
+        the device generator packs (pgx_synth_dict_ids + pgx_inverted_index_build, both release the GIL): a future per
+        (segment, column), submitted in segment order, so the caller stages segment s while later ones are built."""
         from concurrent.futures import ThreadPoolExecutor
         jobs = [(s, ci, c) for s in self.seg_ids for ci, c in enumerate(self.wl.columns) if c.inverted]
         if not jobs:
@@ -297,16 +321,22 @@ class DeviceSegments:
             s, ci, c = job
             ids = np.empty(self.rows, dtype=np.int32)
             N.check(L.pgx_synth_dict_ids(column_seed(self.wl.seed, s, ci), self.rows, c.card, ids.ctypes.data))
+            # one build into a buffer of the format's upper bound: the offsets, per dictId a header and a descriptor
+            # per 64k-doc container, and at most 2 bytes per doc (a bitmap container only replaces a longer array)
+            cap = 4 * (c.card + 1) + c.card * (8 + 8 * ((self.rows + 65535) >> 16)) + 2 * self.rows
             ln = C.c_uint64()
-            N.check(L.pgx_inverted_index_build(ids.ctypes.data, self.rows, c.card, None, 0, C.byref(ln)))
-            buf = bytearray(ln.value)
-            out = (C.c_uint8 * ln.value).from_buffer(buf)
-            N.check(L.pgx_inverted_index_build(ids.ctypes.data, self.rows, c.card, out, ln.value, C.byref(ln)))
+            buf = bytearray(cap)
+            out = (C.c_uint8 * cap).from_buffer(buf)
+            N.check(L.pgx_inverted_index_build(ids.ctypes.data, self.rows, c.card, out, cap, C.byref(ln)))
             del out
-            return (s, ci), bytes(buf)
+            if ln.value > cap:
+                raise RuntimeError("inverted index of %d bytes over the bound of %d" % (ln.value, cap))
+            return bytes(memoryview(buf)[:ln.value])
 
-        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
-            return dict(ex.map(build, jobs))
+        ex = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1))
+        futures = {(s, ci): ex.submit(build, (s, ci, c)) for s, ci, c in jobs}
+        ex.shutdown(wait=False)  # the queued builds still run; the threads end after the last one
+        return futures
 
     def is_inverted(self, name: str) -> bool:
         return any(c.name == name and c.inverted for c in self.wl.columns)
@@ -338,7 +368,8 @@ class DeviceSegments:
         for s in self.segments:
             s.destroy()
         L = N.lib()
-        for p in self.buffers:
+        for p in self.allocs:
             L.pgx_device_free(self.ctx.handle, p)
+        self.allocs = []
         self.buffers = []
         self.segments = []

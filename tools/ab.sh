@@ -9,7 +9,7 @@ for rep in $(seq 1 $REPS); do
   for lib in $LIBS; do
     v=$(basename $lib .so)
     for w in $WLS; do
-      PGX_LIB=$lib timeout -k 10 300 python -u bench.py --workload $w --no-cpu-baseline "$@" > $O/${w}_${v}_$rep.err 2>&1
+      PGX_LIB=$lib timeout -k 10 300 python -u bench.py --full --workload $w --no-cpu-baseline "$@" > $O/${w}_${v}_$rep.err 2>&1
       rc=$?; echo "[$w $v $rep rc=$rc] $(python tools/bench_summary.py $O/${w}_${v}_$rep.err | tr "\n" " ")"
       [ $rc -ne 0 ] && { tail -5 $O/${w}_${v}_$rep.err; exit $rc; }
     done

@@ -10,7 +10,7 @@ WL=${1:-c2}; shift || true
 OUT=gpurun_out/prof_$WL
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o $WL --output-format csv -- \
-  python3 bench.py --workload $WL --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench_under_rocprof.log 2>&1
+  python3 bench.py --full --workload $WL --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench_under_rocprof.log 2>&1
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o $WL --output-format csv -- \
   python3 bench.py --workload $WL --profile-iters 5 "$@" > $OUT/pmc_fetch.log 2>&1
 timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o $WL --output-format csv -- \

@@ -8,8 +8,8 @@ mkdir -p $OUT
 PGX_DEBUG=pf2 timeout -k 10 400 python -u -m pytest tests/test_gpu_partition.py -m gpu -x -q --timeout 120 \
   --timeout-method thread > $OUT/parity_pf2.log 2>&1
 for rep in 1 2; do
-  timeout -k 10 300 python bench.py --workload c3 --no-cpu-baseline > $OUT/c3_pf1_$rep.json 2> $OUT/c3_pf1_$rep.err
-  PGX_DEBUG=pf2 timeout -k 10 300 python bench.py --workload c3 --no-cpu-baseline > $OUT/c3_pf2_$rep.json \
+  timeout -k 10 300 python bench.py --full --workload c3 --no-cpu-baseline > $OUT/c3_pf1_$rep.json 2> $OUT/c3_pf1_$rep.err
+  PGX_DEBUG=pf2 timeout -k 10 300 python bench.py --full --workload c3 --no-cpu-baseline > $OUT/c3_pf2_$rep.json \
     2> $OUT/c3_pf2_$rep.err
 done
 PGX_DEBUG=pf2 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -o c3pf2 -- \

@@ -14,7 +14,7 @@ KLIST=${PGX_PMC_KERNELS:-pgxq+pgx_roaring+pgx_partition+pgx_part_aggregate+pgx_n
 OUT=gpurun_out/prof_$WL
 mkdir -p $OUT
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o $WL --output-format csv -- \
-  python3 bench.py --workload $WL --steps $STEPS --warmup 2 "$@" > $OUT/bench.log 2>&1
+  python3 bench.py --full --workload $WL --steps $STEPS --warmup 2 "$@" > $OUT/bench.log 2>&1
 grep '^{' $OUT/bench.log > $OUT/bench.json
 python3 tools/timeline.py $OUT/trace/${WL}_kernel_trace.csv 1.0 "$KRX" > $OUT/timeline.jsonl
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRX" -d $OUT/pmc_fetch -o $WL --output-format csv -- \
