@@ -48,7 +48,22 @@ constexpr int kN2MaxSub = 1 << kNarrowMaxBits2;
 constexpr int kN2MaxSlabs = 1024;
 constexpr int kN2RingWords = 32768;             // 128 KiB of LDS rings: 32768 >> k2 records per sub-bucket
 constexpr int kN2Unit = 16;                     // records per unit: one 64-byte line segment
-constexpr int kN2ListCap = kN2Chunk / kN2Unit + kN2MaxSub;  // units that can complete in one round
+constexpr int kN2LdsMax = 160 * 1024;            // static LDS a workgroup may use
+// Units that can complete in one round, at W words per record (UR = kN2Unit / W records per unit).  A sub-bucket
+// carries fewer than UR pending records into a round (U is the cursor rounded down to a unit), the round adds kN2Chunk
+// records, and a sub-bucket lists no more than its ring holds: at most
+//   min(nsub * (ring / UR), (nsub * (UR - 1) + kN2Chunk) / UR)
+// units, largest at nsub = kN2MaxSub (the ring is then kN2RingWords / W / kN2MaxSub records): 1472 at W = 1, 1920 at
+// W = 2.  Both are reached (tests/narrow_ref.py worst_case_subs).
+constexpr int n2_list_bound(int W) {
+  const int ur = kN2Unit / W;
+  const int by_ring = kN2MaxSub * (kN2RingWords / W / kN2MaxSub / ur);
+  const int by_records = (kN2MaxSub * (ur - 1) + kN2Chunk) / ur;
+  return by_ring < by_records ? by_ring : by_records;
+}
+// The list's capacity: W = 1 keeps the 1536 entries it always had (>= 1472: its LDS layout is unchanged), W = 2 takes
+// its bound exactly (2048 entries would put the kernel 8 bytes over kN2LdsMax).
+constexpr int n2_list_cap(int W) { return W == 1 ? kN2Chunk / kN2Unit + kN2MaxSub : n2_list_bound(W); }
 
 // Software write combining, as in the scan (pgx_jit.cpp narrow sub-step): sub-bucket s's records take consecutive
 // positions of partition (b << k2 | s) (an LDS cursor per sub-bucket: the atomic returns the position) and wait in the
@@ -74,9 +89,14 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
                                                                unsigned long long* __restrict__ ovf) {
   __shared__ __attribute__((aligned(16))) uint32_t ring[kN2RingWords];
   __shared__ uint32_t cur[kN2MaxSub], Ub[2][kN2MaxSub], Vb[2][kN2MaxSub];
-  __shared__ uint16_t lsub[kN2ListCap];
-  __shared__ uint32_t lpos[kN2ListCap];
+  constexpr int kListCap = n2_list_cap(W);
+  __shared__ uint16_t lsub[kListCap];
+  __shared__ uint32_t lpos[kListCap];
   __shared__ uint32_t lcnt[2];
+  static_assert(kListCap >= n2_list_bound(W), "the unit list must hold every unit that can complete in one round");
+  static_assert(sizeof(ring) + sizeof(cur) + sizeof(Ub) + sizeof(Vb) + sizeof(lsub) + sizeof(lpos) + sizeof(lcnt) <=
+                    kN2LdsMax,
+                "pgx_narrow_split's static LDS exceeds a workgroup's 160 KiB");
   const int b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nsub = 1 << k2;
@@ -693,6 +713,7 @@ __global__ void __launch_bounds__(256) pgx_narrow_compact(const uint64_t* __rest
 // Scratch of the narrow aggregation (pgx_launch_narrow_aggregate): per wavefront, an output region of its partitions x
 // the table size (key + 4 planes), and its row count.
 extern "C" int64_t pgx_narrow_scratch_words(int nparts, int img_kind, int grid) {
+  if (grid < 1) return 0;
   const int64_t nw = int64_t(grid) * (img_kind == 4 ? 16 : 8);
   const int64_t wcap = (int64_t(nparts) + nw - 1) / nw * pgx::kNASlots;
   return nw * wcap * 5 + nw;
@@ -703,9 +724,10 @@ extern "C" hipError_t pgx_launch_narrow_split(const uint32_t* lo, const uint16_t
                                               int64_t cap2, unsigned int* cnt2, unsigned long long* ovf, int wide,
                                               hipStream_t stream) {
   if (nbuckets <= 0) return hipSuccess;
+  // cap2 in whole units: a unit store at p0 < cap2 writes all its records, which must stay inside the partition
   if (nwg < 1 || nwg > pgx::kN2MaxSlabs || k2 < 0 || k2 > pgx::kNarrowMaxBits2 || rb1 - k2 < 0 || rb1 > 48 ||
-      cap1 < 1 || cap1 * nwg >= (int64_t(1) << 32) || cap2 < 1 || cap2 >= (int64_t(1) << 32) || !lo || !out || !cnt1 ||
-      !cnt2 || !ovf)
+      cap1 < 1 || cap1 * nwg >= (int64_t(1) << 32) || cap2 < 1 || cap2 >= (int64_t(1) << 32) ||
+      cap2 % pgx::kN2Unit != 0 || !lo || !out || !cnt1 || !cnt2 || !ovf)
     return hipErrorInvalidValue;
   if (wide)
     hipLaunchKernelGGL(pgx::pgx_narrow_split<2>, dim3(nbuckets), dim3(pgx::kN2Threads), 0, stream, lo, hi, cnt1, nwg,
@@ -724,6 +746,7 @@ extern "C" hipError_t pgx_launch_narrow_aggregate(const uint32_t* in, const unsi
                                                   unsigned long long* prange, int grid, uint64_t* scratch,
                                                   int64_t scratch_words, int wide, hipStream_t stream) {
   if (nparts <= 0) return hipSuccess;
+  if (grid < 1) return hipErrorInvalidValue;  // (before the scratch size, which divides by the grid's wavefronts)
   if (!scratch || scratch_words < pgx_narrow_scratch_words(nparts, img_kind, grid)) return hipErrorInvalidValue;
   const int nw = grid * (img_kind == 4 ? 16 : 8);
   const int64_t wcap = (int64_t(nparts) + nw - 1) / nw * pgx::kNASlots;
