@@ -194,7 +194,12 @@ void build_arena(pgx_ctx* ctx, ExecPlan& P, ExecBuffers& B) {
     // tiles of at least 256 threads x 8 rows (plan_jit may shrink rows per lane per tile to 8 for wide queries)
     if (!P.star.empty() && P.star[s].on) P.star_tile_cap += size_t(P.ksegs[s].num_docs) / 2048 + 2;
   B.off_tiles = align_up(B.off_jsegs + n * sizeof(JSeg), 256);
-  B.off_rdesc = align_up(B.off_tiles + P.star_tile_cap * 4, 256);
+  // leaf slots past the 16 inside KSeg / JSeg (nothing for a filter of at most 16 slots: the layout is unchanged)
+  const size_t nslots = size_t(P.num_leaves) + P.dm_progs.size();
+  B.jxn = nslots > size_t(kInlineLeaves) ? nslots - size_t(kInlineLeaves) : 0;
+  B.off_kxleaf = align_up(B.off_tiles + P.star_tile_cap * 4, 256);
+  B.off_jxleaf = align_up(B.off_kxleaf + P.kxleaf.size() * sizeof(KLeaf), 256);
+  B.off_rdesc = align_up(B.off_jxleaf + n * B.jxn * sizeof(JLeafX), 256);
   B.off_rprog = align_up(B.off_rdesc + P.roar.size() * sizeof(RDesc), 256);
   B.off_outs = align_up(B.off_rprog + P.rprogs.size() * sizeof(RProg), 256);
   const KQuery& K0 = P.kq;
@@ -211,8 +216,8 @@ void build_arena(pgx_ctx* ctx, ExecPlan& P, ExecBuffers& B) {
   for (const auto& f : P.fixes) {
     KSeg& S = P.ksegs[f.seg];
     if (f.kind == 0) S.remap[f.slot] = base + f.off;
-    else if (f.kind == 1) S.leaf[f.slot].ranges = base + f.off;
-    else S.leaf[f.slot].bitset = reinterpret_cast<const uint32_t*>(base + f.off);
+    else if (f.kind == 1) P.leaf(f.seg, f.slot).ranges = base + f.off;
+    else P.leaf(f.seg, f.slot).bitset = reinterpret_cast<const uint32_t*>(base + f.off);
   }
   P.lmask_dev = nullptr;
   if (P.fsm_on) {
@@ -253,7 +258,7 @@ void build_arena(pgx_ctx* ctx, ExecPlan& P, ExecBuffers& B) {
     for (size_t i = 0; i < items.size(); ++i) {
       const auto& it = P.mv_items[i];
       const KSeg& S = P.ksegs[it.seg];
-      const KLeaf& L = S.leaf[it.leaf];
+      const KLeaf& L = P.leaf(it.seg, it.leaf);
       const StagedColumn& col = *P.segcols[it.seg][P.kq.leaf_col[it.leaf]];
       MvLeaf& m = items[i];
       m.vals = col.fwd;
@@ -265,9 +270,15 @@ void build_arena(pgx_ctx* ctx, ExecPlan& P, ExecBuffers& B) {
       m.lo = uint32_t(L.lo);
       m.span = uint32_t(L.hi) - uint32_t(L.lo);
       m.neg = P.mv_neg.empty() ? 0 : P.mv_neg[it.leaf];
-      P.ksegs[it.seg].leaf[it.leaf].bitset = m.mask;  // the query kernel's LEAF_DOCMASK word source
+      P.leaf(it.seg, it.leaf).bitset = m.mask;  // the query kernel's LEAF_DOCMASK word source
     }
     P.mv_descs = DevBuf(ctx, items.size() * sizeof(MvLeaf));
+  }
+  P.kq.xleaf = nullptr;
+  P.kq.xn = P.kxn;
+  if (P.kxn) {
+    P.kq.xleaf = reinterpret_cast<const KLeaf*>(B.dev() + B.off_kxleaf);
+    std::memcpy(B.host.bytes() + B.off_kxleaf, P.kxleaf.data(), P.kxleaf.size() * sizeof(KLeaf));
   }
   if (n) std::memcpy(B.host.bytes() + B.off_ksegs, P.ksegs.data(), n * sizeof(KSeg));
   P.kq.segs = reinterpret_cast<const KSeg*>(B.dev() + B.off_ksegs);
@@ -457,7 +468,7 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     sig.clear();
     for (int l = 0; l < nleaves; ++l)
       sig.push_back(P.roar_index[s][l] >= 0 ? (P.roar[P.roar_index[s][l]].neg ? 101 : 100)
-                                            : (P.mv_index[s][l] >= 0 ? 102 : S.leaf[l].mode));
+                                            : (P.mv_index[s][l] >= 0 ? 102 : P.leaf(s, l).mode));
     if (P.star[s].on) {
       sig.push_back(-7);
       for (size_t i = 0; i < P.star[s].op.size(); ++i) {
@@ -490,7 +501,7 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     J.cols.resize(nc);
     std::vector<bool> dec = decode;
     for (int l = 0; l < nleaves; ++l)
-      if ((S0.leaf[l].mode == LEAF_SCAN_INTERVAL || S0.leaf[l].mode == LEAF_SCAN_BITSET) &&
+      if ((P.leaf(members[0], l).mode == LEAF_SCAN_INTERVAL || P.leaf(members[0], l).mode == LEAF_SCAN_BITSET) &&
           P.roar_index[members[0]][l] < 0 && P.mv_index[members[0]][l] < 0)
         dec[K.leaf_col[l]] = true;
     int R = 8;
@@ -524,6 +535,8 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     // at 32 rows per lane per tile needs ~250 VGPRs for them alone and spills at the 1024-thread workgroups an LDS image
     // asks for: take eight rows per lane (fractional loads of odd widths) and fewer rows per lane per tile until the
     // double-buffered words fit kTileWordBudget.  C2 / C5 shapes (two or three columns) keep 32 rows per lane per tile.
+    // Doc-mask leaves hold double-buffered words per tile as well and are counted with the columns' (many of them lower
+    // TL).
     {
       constexpr int kTileWordBudget = 64;
       auto words = [&](int r) {
@@ -545,7 +558,14 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
         J.R = 8;
         for (JitCol& C : J.cols) C.frac = C.decode && (8 * C.bits) % 32 != 0;
       }
-      const int w = words(J.R);
+      // a doc-mask leaf (a bitmap leaf's or bitmap program's mask, a multi-value leaf's) holds one word per sub-step,
+      // double-buffered like the columns' words (cq<l> / nq<l> in the generated code)
+      int ndm = P.rprog_on && !P.rchunk ? int(P.dm_progs.size()) : 0;
+      for (int l = 0; l < nleaves; ++l) {
+        if (P.rprog_on && P.leaf_phys[l] == PH_BITMAP) continue;  // read via its program
+        if (P.mv_index[members[0]][l] >= 0 || P.roar_index[members[0]][l] >= 0) ++ndm;
+      }
+      const int w = words(J.R) + ndm;
       while (J.TL > J.R && 2 * (J.TL / J.R) * w > kTileWordBudget) J.TL /= 2;
     }
     if (P.kn.no_img && !P.use_part)
@@ -603,6 +623,9 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     J.T = lds <= 20 * 1024 ? 256 : (lds <= 40 * 1024 ? 512 : 1024);
     if (P.rchunk) J.T = 512;  // three 512-thread workgroups per CU, four tiles per chunk
     if (P.use_part) J.T = std::min(J.T, 512);  // record-emitting kernels hold R 64-bit records per lane: 256 VGPRs
+    // more than 16 leaf slots: the rows' predicate loads and doc-mask words do not fit the 128 VGPRs of a 1024-thread
+    // workgroup (the 24-slot selftest shape spills 404 bytes per lane there at any R / TL, nothing at 512 threads)
+    if (nleaves + (P.rprog_on ? int(P.dm_progs.size()) : 0) > kInlineLeaves) J.T = std::min(J.T, 512);
     if (P.part_narrow) {
       // the narrow split's LDS rings (pgx_jit.cpp) want ~16 records per bucket per sub-step (T * R = 4096: a ring of
       // 64 holds the unflushed unit plus the sub-step's records with a wide margin): 512 threads, eight rows per lane
@@ -623,7 +646,8 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
       const int ri = P.roar_index[members[0]][l];
       if (P.rprog_on && P.leaf_phys[l] == PH_BITMAP) J.leaf_mode.push_back(LEAF_NONE);  // read via its program
       else if (P.mv_index[members[0]][l] >= 0) J.leaf_mode.push_back(LEAF_DOCMASK);  // pgx_mv_leaf_mask's doc mask
-      else J.leaf_mode.push_back(ri >= 0 ? (P.roar[ri].neg ? LEAF_DOCMASK_NOT : LEAF_DOCMASK) : S0.leaf[l].mode);
+      else J.leaf_mode.push_back(ri >= 0 ? (P.roar[ri].neg ? LEAF_DOCMASK_NOT : LEAF_DOCMASK)
+                                         : P.leaf(members[0], l).mode);
     }
     if (P.rprog_on)
       for (size_t k = 0; k < P.dm_progs.size(); ++k) {
@@ -755,23 +779,50 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
                        : (P.part_fp || (P.part_narrow && P.narrow_img == 5))
                            ? P.part_fbase[size_t(s)]  // the segment's dictionary in the concatenation / value table
                                    : P.segcols[s][P.part_vcol]->vbase - P.part_vbase;
+      // leaf slots: 0-15 inside the JSeg, the rest in this segment's row of the arena's extension table
+      JLeafX* xs = nullptr;
+      if (B.jxn) {
+        const size_t row = (jidx + G.segs.size()) * B.jxn * sizeof(JLeafX);
+        xs = reinterpret_cast<JLeafX*>(B.host.bytes() + B.off_jxleaf + row);
+        std::memset(xs, 0, B.jxn * sizeof(JLeafX));
+      }
+      auto put = [&](size_t l, const JLeafX& x) {
+        if (l < size_t(kInlineLeaves)) {
+          js.lbits[l] = x.lbits;
+          js.lranges[l] = x.lranges;
+          js.lnr[l] = x.lnr;
+          js.llo[l] = x.llo;
+          js.lspan[l] = x.lspan;
+        } else if (l - size_t(kInlineLeaves) < B.jxn) {
+          xs[l - size_t(kInlineLeaves)] = x;
+        } else {
+          fail(PGX_ERR_INTERNAL, "leaf slot outside the extension table");
+        }
+      };
       if (P.rprog_on)
-        for (size_t k = 0; k < P.dm_progs.size(); ++k)
-          js.lbits[nleaves + k] = P.rchunk ? reinterpret_cast<const uint32_t*>(P.rprog_dev + s * P.dm_progs.size() + k)
-                                           : P.masks_dev + uintptr_t(P.rprogs[size_t(s) * P.dm_progs.size() + k].mask);
+        for (size_t k = 0; k < P.dm_progs.size(); ++k) {
+          JLeafX x{};
+          x.lbits = P.rchunk ? reinterpret_cast<const uint32_t*>(P.rprog_dev + s * P.dm_progs.size() + k)
+                             : P.masks_dev + uintptr_t(P.rprogs[size_t(s) * P.dm_progs.size() + k].mask);
+          put(size_t(nleaves) + k, x);
+        }
       for (int l = 0; l < nleaves; ++l) {
-        const KLeaf& L = S.leaf[l];
+        const KLeaf& L = P.leaf(s, l);
         const int ri = P.roar_index[s][l];
-        js.lbits[l] = (ri >= 0 && !P.rprog_on) ? P.masks_dev + P.roar[ri].mask_off : L.bitset;
-        js.lranges[l] = L.ranges;
-        js.lnr[l] = L.nranges;
-        js.llo[l] = uint32_t(L.lo);
-        js.lspan[l] = uint32_t(L.hi) - uint32_t(L.lo);
+        JLeafX x{};
+        x.lbits = (ri >= 0 && !P.rprog_on) ? P.masks_dev + P.roar[ri].mask_off : L.bitset;
+        x.lranges = L.ranges;
+        x.lnr = L.nranges;
+        x.llo = uint32_t(L.lo);
+        x.lspan = uint32_t(L.hi) - uint32_t(L.lo);
+        put(size_t(l), x);
       }
       if (P.star[s].on)
         for (size_t k = 0; k < P.star[s].ranges.size(); ++k) {
-          js.lranges[nleaves + k] = reinterpret_cast<const int*>(B.dev()) + P.star[s].ranges[k].first;
-          js.lnr[nleaves + k] = P.star[s].ranges[k].second;
+          JLeafX x{};
+          x.lranges = reinterpret_cast<const int*>(B.dev()) + P.star[s].ranges[k].first;
+          x.lnr = P.star[s].ranges[k].second;
+          put(size_t(nleaves) + k, x);
         }
       G.segs.push_back(js);
     }
@@ -785,6 +836,13 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     G.grid = int(std::max<int64_t>(1, (tiles + tpw - 1) / tpw));
     std::memcpy(B.host.bytes() + B.off_jsegs + jidx * sizeof(JSeg), G.segs.data(), G.segs.size() * sizeof(JSeg));
     G.args.segs = reinterpret_cast<const JSeg*>(B.dev() + B.off_jsegs + jidx * sizeof(JSeg));
+    if (B.jxn) {  // the group's rows of the extension table, in the order of its JSegs
+      // (a kernel that reads the table computes its rows with its own slot count)
+      if (J.leaf_col.size() > size_t(kInlineLeaves) && J.leaf_col.size() - size_t(kInlineLeaves) != B.jxn)
+        fail(PGX_ERR_INTERNAL, "leaf-slot extension table row length");
+      G.args.xleaf = reinterpret_cast<const JLeafX*>(B.dev() + B.off_jxleaf + jidx * B.jxn * sizeof(JLeafX));
+      G.xn = int(B.jxn);
+    }
     jidx += G.segs.size();
     G.args.num_segs = int(G.segs.size());
     G.args.rdesc = P.rdesc_dev;
@@ -843,6 +901,7 @@ void launch_scan(ExecPlan& P, hipStream_t st) {
         a.hash_cap = P.kq.hash_cap;
         a.overflow = P.kq.overflow;
         a.segs = G.args.segs + (half ? h : 0);
+        if (G.args.xleaf) a.xleaf = G.args.xleaf + size_t(half ? h : 0) * size_t(G.xn);
         a.num_segs = half ? n - h : h;
         a.tile_base = half ? th : 0;
         a.total_tiles = half ? tiles : th;

@@ -773,7 +773,16 @@ struct ExecPlan {
   bool serial = false;            // planned on a planner thread: no nested parallel_for on the context's pool
   KQuery kq{};
   std::vector<KSeg> ksegs;
-  std::vector<int32_t> blob32;   // ranges / remaps / bitsets, uploaded as one buffer
+  // leaves 16 and up of every segment (filters of more than kInlineLeaves leaves): kxn per segment, uploaded behind
+  // KQuery.xleaf.  leaf(s, l) is the host's store of leaf l of segment s, wherever it lives.
+  std::vector<KLeaf> kxleaf;
+  int kxn = 0;
+  int num_leaves = 0;            // the query's filter leaves
+  KLeaf& leaf(size_t s, int l) {
+    return l < kInlineLeaves ? ksegs[s].leaf[l] : kxleaf[s * size_t(kxn) + size_t(l - kInlineLeaves)];
+  }
+  const KLeaf& leaf(size_t s, int l) const { return const_cast<ExecPlan*>(this)->leaf(s, l); }
+  std::vector<int32_t> blob32;  // ranges / remaps / bitsets, uploaded as one buffer
   struct Fix { size_t seg; int kind; int slot; size_t off; };  // pointer fixups into blob32
   std::vector<Fix> fixes;
   std::vector<std::string> qcols;
@@ -907,6 +916,7 @@ struct ExecPlan {
     int T = 256;
     int grid = 1;
     JArgs args{};
+    int xn = 0;                    // extension-table entries per segment (JArgs.xleaf's row length)
     std::vector<JSeg> segs;
   };
   std::vector<JitGroup> jit;
@@ -963,6 +973,8 @@ struct ExecBuffers {
   DevBuf arena;
   PinnedBuf host;
   size_t off_ksegs = 0, off_jsegs = 0, off_tiles = 0, off_rdesc = 0, off_rprog = 0, off_outs = 0, size = 0;
+  size_t off_kxleaf = 0, off_jxleaf = 0;  // leaf slots past 16: KLeaf x kxn and JLeafX x jxn per segment (empty: none)
+  size_t jxn = 0;
   size_t tbl_bytes = 0;  // in-arena dense table at off_outs + kOutsBytes (0: none)
   bool tbl_live = false;  // this execution's table is the in-arena one (alloc_outputs)
   DevBuf table, keys, key_state, masks;

@@ -10,10 +10,15 @@ constexpr int kTileRows = 8192;        // rows per workgroup tile = 256 lanes x 
 constexpr int kLaneRows = 32;          // rows owned by one lane: exactly one 32-bit mask word
 constexpr int kBlock = 256;            // threads per workgroup
 constexpr int kMaxQCols = 16;          // distinct columns a query touches
-constexpr int kMaxLeaves = 16;
+constexpr int kMaxLeaves = 64;         // filter leaves of one query
+constexpr int kInlineLeaves = PGX_J_MAX_LEAVES;  // leaf slots held inside KSeg / JSeg; the rest behind their xleaf
+constexpr int kMaxLeafSlots = PGX_J_MAX_SLOTS;   // query leaves + bitmap-program masks + star-tree range leaves (the
+                                                 // programs' int8_t arguments index them)
+constexpr int kStarMaxLeaves = 8;      // star-tree plans: query leaves (their range leaves fill slots up to 16)
 constexpr int kMaxAggs = 8;
 constexpr int kMaxGroupCols = 16;
-constexpr int kMaxProg = 64;
+constexpr int kMaxProg = 192;          // generic kernel's program: a tree of L leaves emits at most L leaf ops, L - 1
+                                       // pairwise folds and L OP_STATs, 3 * kMaxLeaves - 1 in all
 constexpr int kStackDepth = 8;
 constexpr uint64_t kEmptyKey = ~0ull;
 
@@ -149,7 +154,7 @@ struct KSeg {
   const void* dict[kMaxQCols];        // value columns: int64 (INT/LONG) or double (FLOAT/DOUBLE) per dictId
   const int32_t* remap[kMaxQCols];    // group columns: dictId -> global id (nullptr = identity)
   int8_t bits[kMaxQCols];
-  KLeaf leaf[kMaxLeaves];
+  KLeaf leaf[kInlineLeaves];          // leaves 0-15 (the rest: KQuery.xleaf)
   uint32_t* lmask;                    // statistics automaton input: leaf l, row r -> bit (r & 31) of
   int64_t lmask_words;                // word [l * lmask_words + (r >> 5)] (nullptr: not requested)
 };
@@ -188,6 +193,9 @@ struct KQuery {
   unsigned long long* keys;      // hash: key_words * hash_cap (word w of slot s at keys[s * key_words + w])
   unsigned int* key_state;       // hash128 / wide: 0 empty, 1 busy, 2 ready
   unsigned long long* overflow;  // hash insert failures (table full) -> host retries bigger
+  // leaves 16 and up: xn per segment, leaf l of segment s at xleaf[s * xn + l - kInlineLeaves] (nullptr: none)
+  const KLeaf* xleaf;
+  int32_t xn;
 };
 
 }  // namespace pgx
@@ -229,7 +237,8 @@ constexpr int kNarrowMaxBits2 = 10;  // second split (pgx_narrow_split): up to 1
 //   PGX_PART_NARROW=0  sparse group-by through the 8-byte radix path instead of the narrow records; =direct: narrow
 //                      records carry value offsets wherever they fit (default: dictIds + LDS image when there is one);
 //                      =gather: integer records carry the dictId's index in a global value table (IMG 5, tests)
-//   PGX_RCHUNK=0|1     bitmap programs evaluated by the separate pass / inside the query kernels (default: planner)
+//   PGX_RCHUNK=0|1     bitmap programs evaluated by the separate pass / inside the query kernels (default: planner;
+//                      programs whose chunk masks do not fit the kernels' LDS budget take the separate pass either way)
 //   PGX_RPROG=off|wave|seg|chunk|stack   bitmap-program kernel (off: no program fusion; default: planner)
 //   PGX_BATCH_SEGS=N   segments per batch of a long segment list on its first execution (0: one launch)
 //   PGX_DEBUG=opt,...  part_small (radix buckets start undersized), narrow_k2=N (coarser narrow partitions),

@@ -340,25 +340,31 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
   for (int c = 0; c < ncols; ++c)
     if (s.cols[c].decode) e.ln("const u32* __restrict__ f", c, " = pgx_sgpr(S->fwd[", c, "]);");
   const int nleaves = int(s.leaf_col.size());
+  // slot l's field: inside JSeg for slots 0-15, in the segment's row of the extension table (JArgs.xleaf) past them
+  auto slot = [&](const char* field, int l) {
+    if (l < PGX_J_MAX_LEAVES) return "S->" + std::string(field) + "[" + std::to_string(l) + "]";
+    return "A.xleaf[(long long)seg * " + std::to_string(nleaves - PGX_J_MAX_LEAVES) + " + " +
+           std::to_string(l - PGX_J_MAX_LEAVES) + "]." + field;
+  };
   for (int l = 0; l < nleaves; ++l) {
     switch (s.leaf_mode[l]) {
       case LEAF_SCAN_INTERVAL:
-        e.ln("const u32 lo", l, " = S->llo[", l, "], sp", l, " = S->lspan[", l, "];");
+        e.ln("const u32 lo", l, " = ", slot("llo", l), ", sp", l, " = ", slot("lspan", l), ";");
         break;
       case LEAF_SCAN_BITSET:
-        e.ln("const PGX_G u32* __restrict__ bs", l, " = (const PGX_G u32*)S->lbits[", l, "];");
+        e.ln("const PGX_G u32* __restrict__ bs", l, " = (const PGX_G u32*)", slot("lbits", l), ";");
         break;
       case LEAF_DOCMASK:
       case LEAF_DOCMASK_NOT:
-        e.ln("const PGX_G u32* __restrict__ dm", l, " = (const PGX_G u32*)S->lbits[", l, "];");
+        e.ln("const PGX_G u32* __restrict__ dm", l, " = (const PGX_G u32*)", slot("lbits", l), ";");
         break;
       case LEAF_RCHUNK:
-        e.ln("const PGX_G JRProg* __restrict__ rp", l, " = (const PGX_G JRProg*)S->lbits[", l, "];");
+        e.ln("const PGX_G JRProg* __restrict__ rp", l, " = (const PGX_G JRProg*)", slot("lbits", l), ";");
         e.ln("u32* const rlm", l, " = lds + ", rch_off[l] / 4, ";");
         break;
       case LEAF_RANGES:
-        e.ln("const PGX_G int* __restrict__ rg", l, " = (const PGX_G int*)S->lranges[", l, "];");
-        e.ln("const int nr", l, " = S->lnr[", l, "];");
+        e.ln("const PGX_G int* __restrict__ rg", l, " = (const PGX_G int*)", slot("lranges", l), ";");
+        e.ln("const int nr", l, " = ", slot("lnr", l), ";");
         e.ln("int cur", l, " = pgx_ranges_seek(rg", l, ", nr", l, ", (int)((tl ? (long long)tl[t - tile0] : (t - tile0)) * (PT * PTL)));");
         break;
       default:
@@ -1790,6 +1796,78 @@ extern "C" int pgx_jit_selftest(int* n_total, char* log, unsigned long log_cap) 
     s.num_planes = 2;
     s.cols[1].decode = false;
     s.cols[1].img = IMG_NONE;
+    shapes.push_back(s);
+  }
+  // Filters of more than 16 leaf slots: slots 16 and up are read from the extension table (JArgs.xleaf).
+  // R / TL as plan_jit's tile-word budget sets them for these columns and doc-mask counts.
+  auto fold_all = [](JitShape& s, int first, int n, int op) {  // slots first .. first + n - 1 under pairwise folds
+    for (int l = first; l < first + n; ++l) {
+      s.prog_op.push_back(OP_LEAF);
+      s.prog_arg.push_back(l);
+      if (l > first) {
+        s.prog_op.push_back(op);
+        s.prog_arg.push_back(2);
+      }
+    }
+  };
+  {  // 40 scan leaves (interval and bitset) over three columns (8, 7 and 12 bits) under one OR
+    JitShape s = base(8, 16, IMG_U32, 0);
+    s.cols.resize(4);
+    s.cols[2].bits = 7;
+    s.cols[3].bits = 12;
+    s.cols[2].decode = s.cols[3].decode = true;
+    s.R = 8;
+    s.TL = 16;
+    for (JitCol& C : s.cols) C.frac = C.decode && (8 * C.bits) % 32 != 0;
+    s.leaf_col.clear();
+    s.leaf_mode.clear();
+    s.prog_op.clear();
+    s.prog_arg.clear();
+    for (int l = 0; l < 40; ++l) {
+      s.leaf_col.push_back(l % 3 == 0 ? 0 : 1 + l % 3);
+      s.leaf_mode.push_back(l % 2 ? LEAF_SCAN_BITSET : LEAF_SCAN_INTERVAL);
+    }
+    fold_all(s, 0, 40, OP_OR);
+    shapes.push_back(s);
+  }
+  {  // 24 slots: 16 scan leaves, then 8 doc masks (one negated), under one OR
+    JitShape s = base(10, 16, IMG_FOR16, 11);
+    s.R = 16;
+    s.TL = 16;
+    s.T = 512;  // (plan_jit: more than 16 slots never run at 1024 threads, whose 128 VGPRs spill here)
+    s.leaf_col.clear();
+    s.leaf_mode.clear();
+    s.prog_op.clear();
+    s.prog_arg.clear();
+    for (int l = 0; l < 24; ++l) {
+      s.leaf_col.push_back(l < 16 ? 0 : -1);
+      s.leaf_mode.push_back(l < 16 ? (l % 2 ? LEAF_SCAN_BITSET : LEAF_SCAN_INTERVAL)
+                                   : (l == 19 ? LEAF_DOCMASK_NOT : LEAF_DOCMASK));
+    }
+    fold_all(s, 0, 24, OP_OR);
+    shapes.push_back(s);
+  }
+  {  // sorted ranges AND a doc mask (slots 20, 21), then 20 scan leaves with their OP_STATs
+    JitShape s = base(8, 16, IMG_U32, 0);
+    s.cols.resize(3);
+    s.cols[2].bits = 7;
+    s.cols[2].decode = true;
+    s.R = 32;
+    s.TL = 32;
+    s.leaf_col.clear();
+    s.leaf_mode.clear();
+    for (int l = 0; l < 20; ++l) {
+      s.leaf_col.push_back(l % 2 ? 2 : 0);
+      s.leaf_mode.push_back(l % 4 == 3 ? LEAF_SCAN_BITSET : LEAF_SCAN_INTERVAL);
+    }
+    s.leaf_col.insert(s.leaf_col.end(), {-1, -1});
+    s.leaf_mode.insert(s.leaf_mode.end(), {LEAF_RANGES, LEAF_DOCMASK});
+    s.prog_op = {OP_LEAF, OP_LEAF, OP_AND};
+    s.prog_arg = {20, 21, 2};
+    for (int l = 0; l < 20; ++l) {
+      s.prog_op.insert(s.prog_op.end(), {OP_STAT, OP_LEAF, OP_AND});
+      s.prog_arg.insert(s.prog_arg.end(), {0, l, 2});
+    }
     shapes.push_back(s);
   }
   int failed = 0;

@@ -5,7 +5,8 @@
 #define PGX_JIT_ABI_H_
 
 #define PGX_J_MAX_COLS 16    // distinct columns one generated kernel reads (== kMaxQCols)
-#define PGX_J_MAX_LEAVES 16  // filter leaves (== kMaxLeaves)
+#define PGX_J_MAX_LEAVES 16  // leaf slots held inside JSeg (== kInlineLeaves); slots 16 and up: JArgs.xleaf
+#define PGX_J_MAX_SLOTS 96   // leaf slots of one kernel: query leaves + bitmap-program masks + star-tree range leaves
 #define PGX_J_MAX_AGGS 8     // aggregation functions (== kMaxAggs)
 
 // Bitmap inverted-index leaf of one segment: the roaring bitmaps (byte offsets into the staged .bitmap.inv) whose OR
@@ -29,6 +30,21 @@ struct JRProg {
   signed char op[PGX_J_MAX_RPROG];   // 0 leaf, 1 AND, 2 OR, 3 NOT
   short arg[PGX_J_MAX_RPROG];        // leaf: index into the JRDesc array (-1: empty leaf)
   short ldesc[PGX_J_MAX_RLEAVES];    // the leaves' arg values in program order (LEAF_RCHUNK)
+};
+
+// Leaf slots past PGX_J_MAX_LEAVES (filters of more than 16 slots): one entry per slot, the same five fields JSeg holds
+// for slots 0-15.  The launch group's entries sit in the argument arena behind JArgs.xleaf, a row of (slots - 16)
+// entries per segment in JSeg order: slot l of segment i at xleaf[i * (slots - 16) + l - PGX_J_MAX_LEAVES].  The
+// generated code reads a slot from JSeg or from here by the slot's number, known when the kernel is generated.  JSeg
+// itself is the same for every query (a pointer per segment in it measured 0.45% slower at C5, whose queries send 4,096
+// JSegs: DESIGN 3.16), so a query of at most 16 slots pays one unused kernel argument and nothing per segment.
+struct JLeafX {
+  const unsigned int* lbits;
+  const int* lranges;
+  int lnr;
+  unsigned int llo;
+  unsigned int lspan;
+  int pad0;
 };
 
 // Per-segment arguments of one launch group (segments whose columns share bit widths and value-image kinds).
@@ -79,6 +95,7 @@ struct JArgs {
   long long hash_cap;                // its slots (a power of two; planes at table + p * hash_cap)
   unsigned long long* overflow;      // keys that found no global slot (the host grows the table and reruns)
   long long tile_base;               // first tile of this launch (a plan launched in two halves: the second half's)
+  const struct JLeafX* xleaf;        // leaf slots 16 and up of segs[0], segs[1], ... (0: at most 16 slots)
 };
 
 #endif  // PGX_JIT_ABI_H_

@@ -128,9 +128,9 @@ __device__ __forceinline__ uint32_t ranges_word(const KLeaf& L, int32_t row0) {
   return word;
 }
 
-__device__ __forceinline__ uint32_t leaf_word(const KSeg& S, const KQuery& Q, int leaf, int32_t row0,
+__device__ __forceinline__ uint32_t leaf_word(const KSeg& S, const KLeaf* xl, const KQuery& Q, int leaf, int32_t row0,
                                               int64_t lane_chunk) {
-  const KLeaf& L = S.leaf[leaf];
+  const KLeaf& L = leaf < kInlineLeaves ? S.leaf[leaf] : xl[leaf - kInlineLeaves];
   if (L.mode == LEAF_NONE) return 0u;
   if (L.mode == LEAF_RANGES) return ranges_word(L, row0);
   const int c = Q.leaf_col[leaf];
@@ -162,15 +162,16 @@ struct WordStack {
   }
 };
 
-__device__ __forceinline__ uint32_t run_filter(const KSeg& S, const KQuery& Q, int32_t row0, int64_t lane_chunk,
-                                               uint32_t valid, unsigned long long& entries) {
+// xl: the segment's leaves 16 and up (KQuery.xleaf's row of it)
+__device__ __forceinline__ uint32_t run_filter(const KSeg& S, const KLeaf* xl, const KQuery& Q, int32_t row0,
+                                               int64_t lane_chunk, uint32_t valid, unsigned long long& entries) {
   if (Q.prog_len == 0) return valid;
   WordStack st;
   for (int pc = 0; pc < Q.prog_len; ++pc) {
     const int op = Q.prog_op[pc];
     const int arg = Q.prog_arg[pc];
     if (op == OP_LEAF) {
-      const uint32_t w = leaf_word(S, Q, arg, row0, lane_chunk) & valid;
+      const uint32_t w = leaf_word(S, xl, Q, arg, row0, lane_chunk) & valid;
       if (S.lmask) S.lmask[arg * S.lmask_words + lane_chunk] = w;  // statistics automaton input
       st.push(w);
     } else if (op == OP_AND) {
@@ -359,7 +360,8 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
     else valid = (1u << (S.num_docs - row0)) - 1u;
 
     uint32_t mask = 0;
-    if (valid) mask = run_filter(S, Q, row0, lane_chunk, valid, entries);
+    const KLeaf* xl = Q.xleaf ? Q.xleaf + static_cast<int64_t>(seg) * Q.xn : nullptr;
+    if (valid) mask = run_filter(S, xl, Q, row0, lane_chunk, valid, entries);
     docs += __popc(mask);
 
     if constexpr (GM == G_NONE) {

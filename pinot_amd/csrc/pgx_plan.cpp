@@ -507,11 +507,22 @@ bool stats_closed_form(const PNode& root, const pgx_query& q, pgx_segment* const
 }
 
 // Bitmap sub-trees: a node whose leaves are all bitmap inverted-index leaves (and the bitmap / all-bitmap children of
-// any AND / OR) is evaluated per 65536-doc chunk by pgx_roaring_program into ONE doc mask.
+// any AND / OR) is evaluated per 65536-doc chunk by pgx_roaring_program into ONE doc mask.  One program holds at most
+// kMaxRProg ops (a NEQ / NOT_IN leaf's RP_NOT included), a stack of kRProgDepth masks and, where the query kernels
+// evaluate it themselves (LEAF_RCHUNK), PGX_J_MAX_RLEAVES leaves.  An AND / OR whose all-bitmap children exceed that is
+// split at that node (AND and OR are associative): consecutive children that fit together become one program and one
+// doc-mask leaf, a child too large on its own is split the same way, and the node's operator joins the parts' masks
+// in the query program.
+constexpr int kRProgDepth = 4;
 struct FusePlan {
-  std::map<const PNode*, int> full;   // node evaluated whole by program k
-  std::map<const PNode*, int> group;  // AND / OR whose all-bitmap children are program k
+  struct Part {
+    int prog;            // program whose mask stands for a run of children, or -1:
+    const PNode* node;   // a child split further (parts[node]), joined by its own operator
+  };
+  std::map<const PNode*, int> full;                 // node evaluated whole by program k
+  std::map<const PNode*, std::vector<Part>> parts;  // AND / OR: what stands where its all-bitmap children were
   std::vector<ExecPlan::DmProg> progs;
+  int max_leaves = kMaxRProg;                       // leaves of one program
 };
 
 bool all_bitmap(const PNode& n) {
@@ -541,6 +552,78 @@ void bitmap_prog(const PNode& n, const pgx_query& q, ExecPlan::DmProg& p) {
   }
 }
 
+// What bitmap_prog(n) costs: ops, the deepest mask stack (children fold pairwise: the i-th child is evaluated above
+// the running result), leaves.
+struct ProgCost {
+  int ops = 0, depth = 0, leaves = 0;
+};
+ProgCost prog_cost(const PNode& n, const pgx_query& q) {
+  ProgCost c;
+  if (n.op == PGX_F_LEAF) {
+    c.ops = 1 + (q.leaf_kind[n.leaf] == PGX_PRED_NEQ || q.leaf_kind[n.leaf] == PGX_PRED_NOT_IN);
+    c.depth = c.leaves = 1;
+    return c;
+  }
+  for (size_t i = 0; i < n.kids.size(); ++i) {
+    const ProgCost k = prog_cost(n.kids[i], q);
+    c.ops += k.ops + (i > 0);
+    c.depth = std::max(c.depth, k.depth + (i > 0));
+    c.leaves += k.leaves;
+  }
+  return c;
+}
+bool prog_fits(const ProgCost& c, const FusePlan& F) {
+  return c.ops <= kMaxRProg && c.depth <= kRProgDepth && c.leaves <= F.max_leaves;
+}
+
+void fuse_split(const PNode& n, const pgx_query& q, FusePlan& F);
+
+// The all-bitmap children `kids` of an AND / OR (`op`), packed in order into as few programs as hold them.
+std::vector<FusePlan::Part> fuse_pack(const std::vector<const PNode*>& kids, int op, const pgx_query& q, FusePlan& F) {
+  std::vector<FusePlan::Part> out;
+  ExecPlan::DmProg cur;
+  ProgCost cc;
+  int ng = 0;  // children in cur
+  auto close = [&]() {
+    if (!ng) return;
+    out.push_back({int(F.progs.size()), nullptr});
+    F.progs.push_back(std::move(cur));
+    cur = ExecPlan::DmProg{};
+    cc = ProgCost{};
+    ng = 0;
+  };
+  for (const PNode* k : kids) {
+    const ProgCost kc = prog_cost(*k, q);
+    if (!prog_fits(kc, F)) {  // (an AND / OR: a leaf is at most two ops)
+      close();
+      fuse_split(*k, q, F);
+      out.push_back({-1, k});
+      continue;
+    }
+    ProgCost nc{cc.ops + kc.ops + (ng > 0), std::max(cc.depth, kc.depth + (ng > 0)), cc.leaves + kc.leaves};
+    if (ng && !prog_fits(nc, F)) {
+      close();
+      nc = kc;
+    }
+    bitmap_prog(*k, q, cur);
+    if (ng) {
+      cur.op.push_back(op == PGX_F_AND ? RP_AND : RP_OR);
+      cur.arg.push_back(0);
+    }
+    cc = nc;
+    ++ng;
+  }
+  close();
+  return out;
+}
+
+// An all-bitmap AND / OR that does not fit one program.
+void fuse_split(const PNode& n, const pgx_query& q, FusePlan& F) {
+  std::vector<const PNode*> kids;
+  for (const PNode& k : n.kids) kids.push_back(&k);
+  F.parts[&n] = fuse_pack(kids, n.op, q, F);
+}
+
 void plan_fuse(const PNode& n, const pgx_query& q, FusePlan& F) {
   if (n.op == PGX_F_LEAF) {
     if (n.phys == PH_BITMAP) {
@@ -551,6 +634,10 @@ void plan_fuse(const PNode& n, const pgx_query& q, FusePlan& F) {
     return;
   }
   if (all_bitmap(n)) {
+    if (!prog_fits(prog_cost(n, q), F)) {
+      fuse_split(n, q, F);
+      return;
+    }
     F.full[&n] = int(F.progs.size());
     F.progs.emplace_back();
     bitmap_prog(n, q, F.progs.back());
@@ -562,16 +649,7 @@ void plan_fuse(const PNode& n, const pgx_query& q, FusePlan& F) {
     else plan_fuse(k, q, F);
   }
   if (fk.empty()) return;
-  ExecPlan::DmProg p;
-  for (size_t i = 0; i < fk.size(); ++i) {
-    bitmap_prog(*fk[i], q, p);
-    if (i > 0) {
-      p.op.push_back(n.op == PGX_F_AND ? RP_AND : RP_OR);
-      p.arg.push_back(0);
-    }
-  }
-  F.group[&n] = int(F.progs.size());
-  F.progs.push_back(std::move(p));
+  F.parts[&n] = fuse_pack(fk, n.op, q, F);
 }
 
 int prog_depth(const ExecPlan::DmProg& p) {
@@ -583,8 +661,27 @@ int prog_depth(const ExecPlan::DmProg& p) {
   return mx;
 }
 
-// emit() with bitmap programs: a fused node is one doc-mask leaf (query leaf L + k); an AND / OR puts its fused group
-// where its bitmap children were (AND: after the sorted ranges, before the scan children and their OP_STATs).
+// The doc-mask leaves of a node's fused parts, each folded into the running result with the node's operator (opc).
+void emit_parts(const std::vector<FusePlan::Part>& parts, int opc, const FusePlan& F, int L, std::vector<int8_t>& op,
+                std::vector<int8_t>& arg, int& pushed) {
+  for (const FusePlan::Part& p : parts) {
+    if (p.prog >= 0) {
+      op.push_back(OP_LEAF);
+      arg.push_back(int8_t(L + p.prog));
+    } else {
+      int inner = 0;
+      emit_parts(F.parts.at(p.node), p.node->op == PGX_F_AND ? OP_AND : OP_OR, F, L, op, arg, inner);
+    }
+    if (++pushed > 1) {
+      op.push_back(int8_t(opc));
+      arg.push_back(2);
+    }
+  }
+}
+
+// emit() with bitmap programs: a fused node is one doc-mask leaf (query leaf L + k), or several joined by its operator
+// when it was split; an AND / OR puts its fused parts where its bitmap children were (AND: after the sorted ranges,
+// before the scan children and their OP_STATs).
 void emit_fused(const PNode& n, const FusePlan& F, int L, std::vector<int8_t>& op, std::vector<int8_t>& arg, bool root,
                 int& host_scan_leaves) {
   auto f = F.full.find(&n);
@@ -599,11 +696,15 @@ void emit_fused(const PNode& n, const FusePlan& F, int L, std::vector<int8_t>& o
     if (root && n.phys == PH_SCAN) host_scan_leaves += 1;
     return;
   }
-  auto g = F.group.find(&n);
+  auto g = F.parts.find(&n);
   int pushed = 0;
   auto fold = [&](int opc) {
     if (pushed > 1) { op.push_back(int8_t(opc)); arg.push_back(2); }
   };
+  if (g != F.parts.end() && all_bitmap(n)) {  // an all-bitmap node split into several programs
+    emit_parts(g->second, n.op == PGX_F_AND ? OP_AND : OP_OR, F, L, op, arg, pushed);
+    return;
+  }
   if (n.op == PGX_F_OR) {
     for (const PNode& k : n.kids) {
       if (all_bitmap(k)) continue;
@@ -612,12 +713,7 @@ void emit_fused(const PNode& n, const FusePlan& F, int L, std::vector<int8_t>& o
       ++pushed;
       fold(OP_OR);
     }
-    if (g != F.group.end()) {
-      op.push_back(OP_LEAF);
-      arg.push_back(int8_t(L + g->second));
-      ++pushed;
-      fold(OP_OR);
-    }
+    if (g != F.parts.end()) emit_parts(g->second, OP_OR, F, L, op, arg, pushed);
     return;
   }
   for (const PNode& k : n.kids)
@@ -626,12 +722,7 @@ void emit_fused(const PNode& n, const FusePlan& F, int L, std::vector<int8_t>& o
       ++pushed;
       fold(OP_AND);
     }
-  if (g != F.group.end()) {
-    op.push_back(OP_LEAF);
-    arg.push_back(int8_t(L + g->second));
-    ++pushed;
-    fold(OP_AND);
-  }
+  if (g != F.parts.end()) emit_parts(g->second, OP_AND, F, L, op, arg, pushed);
   const bool fast = pushed > 0;
   for (const PNode& k : n.kids)
     if (k.op == PGX_F_LEAF && k.phys == PH_SCAN) {
@@ -782,8 +873,11 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   if (n < 1) fail(PGX_ERR_INVALID_ARG, "no segments");
   if (q.agg_fn.size() > size_t(kMaxAggs)) fail(PGX_ERR_UNSUPPORTED, "too many aggregation functions");
   if (q.group_cols.size() > size_t(kMaxGroupCols)) fail(PGX_ERR_UNSUPPORTED, "too many group-by columns");
-  if (q.leaf_col.size() > size_t(kMaxLeaves)) fail(PGX_ERR_UNSUPPORTED, "too many filter leaves");
+  if (q.leaf_col.size() > size_t(kMaxLeaves))
+    fail(PGX_ERR_UNSUPPORTED, "too many filter leaves: " + std::to_string(q.leaf_col.size()) + " (the limit is " +
+                                  std::to_string(kMaxLeaves) + ")");
   P.kn = q.kn;
+  P.num_leaves = int(q.leaf_col.size());
   KQuery& K = P.kq;
   // query column slots
   for (size_t l = 0; l < q.leaf_col.size(); ++l) K.leaf_col[l] = int8_t(qslot(P, q.leaf_col[l]));
@@ -1199,11 +1293,13 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
     }
     prof_mark("p.fusechk");
     FusePlan F;
+    // (PGX_RCHUNK=1: every program must also fit the query kernels' in-LDS evaluation)
+    if (q.kn.rchunk == 1) F.max_leaves = PGX_J_MAX_RLEAVES;
     if (fuse) {
       plan_fuse(root, q, F);
-      if (F.progs.empty() || L + F.progs.size() > size_t(PGX_J_MAX_LEAVES)) fuse = false;
-      for (const auto& p : F.progs)
-        if (prog_depth(p) > 4 || p.op.size() > size_t(kMaxRProg)) fuse = false;
+      if (F.progs.empty() || L + F.progs.size() > size_t(kMaxLeafSlots)) fuse = false;
+      for (const auto& p : F.progs)  // (plan_fuse splits what would not fit)
+        if (prog_depth(p) > kRProgDepth || p.op.size() > size_t(kMaxRProg)) fuse = false;
     }
     if (fuse) {
       emit_fused(root, F, int(L), pop, parg, true, host_scan_leaves);
@@ -1214,7 +1310,11 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
       emit(root, pop, parg, true, false, host_scan_leaves);
     }
     if (!stats_closed_form(root, q, segs, n, bindings)) {
-      // the automaton counts every entry: no OP_STAT popcounts, no whole-range host terms
+      // the automaton counts every entry: no OP_STAT popcounts, no whole-range host terms.  Its tables are indexed by
+      // every leaf's membership bit and its per-segment leaf masks are 32-bit words: refuse before any of them is made
+      if (L > size_t(kFsmMaxLeaves))
+        fail(PGX_ERR_UNSUPPORTED,
+             "filter statistics automaton: more than " + std::to_string(kFsmMaxLeaves) + " leaves");
       P.fsm_on = true;
       host_scan_leaves = 0;
       std::vector<int8_t> o2, a2;
@@ -1251,6 +1351,8 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   // per-segment descriptors: planned in chunks of segments (in parallel for long segment lists); each chunk keeps its
   // blob words, pointer fixups and bitmap items with chunk-local offsets, concatenated in segment order afterwards.
   P.ksegs.assign(n, KSeg{});
+  P.kxn = std::max(0, P.num_leaves - kInlineLeaves);
+  P.kxleaf.assign(size_t(n) * size_t(P.kxn), KLeaf{});
   P.segcols.assign(n, {});
   P.sorted_span.assign(size_t(n) * q.leaf_col.size(), 0);
   // Per distinct (leaf, binding, cardinality) in a chunk: the leaf mode, ONE blob copy of its dictId bitset and ONE list
@@ -1312,7 +1414,7 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
       for (size_t l = 0; l < q.leaf_col.size(); ++l) {
         const StagedColumn& col = *segcols[K.leaf_col[l]];
         const pgx_leaf_binding& b = bindings[size_t(s) * q.leaf_col.size() + l];
-        KLeaf& L = S.leaf[l];
+        KLeaf& L = P.leaf(size_t(s), int(l));
         L.lo = b.lo;
         L.hi = b.hi;
         L.bitset = nullptr;
@@ -1476,6 +1578,20 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
     }
     P.rchunk = est <= kRchunkMaxSel;
     if (q.kn.rchunk >= 0) P.rchunk = q.kn.rchunk == 1;
+    if (P.rchunk) {
+      // the in-kernel evaluation keeps one 8 KiB chunk mask per program leaf in LDS, inside a 52 KiB budget (plan_jit)
+      // with the container-search scratch and the group table: what does not fit takes the separate pass
+      int64_t bytes = 5152;
+      if (K.group_mode == G_DENSE_LDS) bytes += int64_t(P.dense_slots) * K.num_planes * 8;
+      if (K.group_mode == G_HASH64 || K.group_mode == G_HASH128)
+        bytes += 512 * ((K.group_mode == G_HASH128 ? 20 : 8) + 8 * int64_t(K.num_planes)) + 32;
+      for (const auto& dp : P.dm_progs) {
+        const int64_t nl = std::count(dp.op.begin(), dp.op.end(), int(RP_LEAF));
+        if (nl > PGX_J_MAX_RLEAVES) bytes = INT64_MAX / 2;
+        bytes += nl * 8192;
+      }
+      if (bytes > 52 * 1024) P.rchunk = false;
+    }
     for (int s = 0; s < n && P.rchunk; ++s)
       if (star_fit(q, *segs[s])) P.rchunk = false;
   }
@@ -1518,13 +1634,13 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   prof_mark("p.merge");
   // star-tree segments (query kernels only: the per-segment program needs the generated kernels)
   P.star.assign(n, ExecPlan::StarPlan{});
-  if (P.use_docmask && !P.use_part && int(q.leaf_col.size()) + 8 <= PGX_J_MAX_LEAVES) {
+  if (P.use_docmask && !P.use_part && int(q.leaf_col.size()) <= kStarMaxLeaves) {
     tiles = 0;
     for (int s = 0; s < n; ++s) {
       KSeg& S = P.ksegs[s];
       if (star_fit(q, *segs[s])) {
         plan_star_segment(q, *segs[s], S, bindings + size_t(s) * q.leaf_col.size(), P.leaf_phys, P.blob32, P.star[s]);
-        if (int(q.leaf_col.size() + P.star[s].ranges.size()) > PGX_J_MAX_LEAVES) {
+        if (int(q.leaf_col.size() + P.star[s].ranges.size()) > kInlineLeaves) {
           P.star[s] = ExecPlan::StarPlan{};
         } else {
           // StarTreeIndexOperator reaches aggregated docs: scan [0, totalDocs); no root scan leaf
@@ -1560,7 +1676,7 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
           si.sorted_first[l] = sp >> 32;
           si.sorted_last[l] = int32_t(uint32_t(sp));
         }
-        if (P.ksegs[s].leaf[l].mode == LEAF_NONE && P.leaf_phys[l] == PH_SCAN) si.always_false |= 1u << l;
+        if (P.leaf(size_t(s), l).mode == LEAF_NONE && P.leaf_phys[l] == PH_SCAN) si.always_false |= 1u << l;
       }
       infos.push_back(std::move(si));
       fsegs.push_back(s);
