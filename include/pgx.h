@@ -17,6 +17,10 @@
  *                          AggregationGroupByResult.getResultForKey, ExecutionStatistics)
  *   pgx_leaf_binding    <- operator/filter/predicate/PredicateEvaluator.getMatchingDictionaryIds (the caller's
  *                          PredicateEvaluatorProvider resolves each predicate to dictId space per segment)
+ *   pgx_select_compile, <- plan/SelectionPlanNode.java -> operator/MSelectionOrderByOperator.java:59-124 over
+ *   pgx_result_select_*    query/selection/SelectionOperatorService.java (the per-segment PriorityQueue of offset + size
+ *                          docs under CompositeDocIdValComparator, iterator/DocIdIntValComparator) and
+ *                          query/selection/SelectionOperatorUtils.java:223-253 (extractDataSchema)
  *
  * Conventions: every call returns pgx_status (0 = OK); no C++ exception crosses the ABI; on error
  * pgx_last_error() returns a thread-local message.  Plain pointers and sizes only.  A pgx_ctx is
@@ -34,7 +38,9 @@ extern "C" {
 #endif
 
 #define PGX_ABI_VERSION 8  /* 7: pgx_mutable_* (realtime segments in place); 8: pgx_result_record_words, records of
-                              * every device-resident layout (several value columns, f64 sums) */
+                              * every device-resident layout (several value columns, f64 sums); pgx_select_compile and
+                              * pgx_result_select_* were added under 8: new entry points only, no existing struct or
+                              * call changed */
 
 typedef enum {
   PGX_OK = 0,
@@ -196,6 +202,47 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* desc, pgx_query
 pgx_status pgx_query_set_key_domain(pgx_query* q, int32_t group_col, int32_t type, int64_t num_values,
                                     const int64_t* ivals, const double* dvals, const char* const* svals);
 pgx_status pgx_query_release(pgx_query* q);
+
+/* ---- selection with ORDER BY --------------------------------------------------------------------
+ * SELECT cols | * FROM t [WHERE ...] ORDER BY c1 [ASC|DESC], ... LIMIT [offset,] size.  The resulting pgx_query works
+ * with pgx_bind_predicates, pgx_execute, pgx_execute_async, pgx_result_stats, pgx_result_wait and pgx_query_release.
+ * Per segment the rows rank by (order key, docId) ascending: the key is the order columns' dictIds (v1 dictionaries are
+ * sorted; DESC takes cardinality - 1 - dictId), max(1, ceil(log2 cardinality)) bits each, most significant first; the
+ * docId as last component makes the result unique (the reference's choice among ties at the boundary follows
+ * java.util.PriorityQueue's heap order).  PGX_ERR_UNSUPPORTED (the caller falls back to the Java operators): no ORDER
+ * BY (MSelectionOnlyOperator), more than 8 order columns, a key wider than 64 bits, offset + size of 0 or above
+ * PGX_SEL_MAX_ROWS, a multi-value column among the order or selected columns, pgx_execute_multi, key domains, dense
+ * outputs, pgx_execute_timed.  Selection runs never use a star tree (every raw row is ranked).  The data schema is
+ * that of SelectionOperatorUtils.extractDataSchema: the order columns in ORDER BY order, then the selected columns
+ * sorted by name, minus those already present; "*" is the first segment's columns. */
+#define PGX_SEL_MAX_ROWS 2048
+typedef struct {
+  const char* column;
+  int32_t ascending;
+} pgx_order_by;
+typedef struct {
+  int32_t num_columns;
+  const char* const* columns; /* as written; a single "*" = all columns */
+  int32_t num_order_by;       /* >= 1 */
+  const pgx_order_by* order_by;
+  int32_t offset, size;       /* LIMIT offset, size */
+  int32_t num_filter_nodes;
+  const pgx_filter_node* filter;
+  int32_t num_leaves;
+  const pgx_leaf* leaves;
+  uint32_t flags;             /* PGX_Q_* */
+} pgx_select_desc;
+pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* desc, pgx_query** out);
+/* Selection results: per segment its best <= offset + size rows, best first; the caller merges the segments' lists by
+ * value (MCombineOperator -> SelectionOperatorService.mergeWithOrdering in the reference: dictIds of different segments
+ * do not compare).  They return PGX_ERR_INVALID_ARG on an aggregation or group-by result, as pgx_result_agg and the
+ * group accessors do on a selection result.
+ * schema: *num_columns, and names[c] (may be NULL; the strings live as long as the result).
+ * counts: rows_per_segment[n].  rows: the segments' rows back to back (total = sum of the counts): seg_index[row],
+ * doc_id[row], dict_ids[c * total + row] for schema column c.  Any output may be NULL. */
+pgx_status pgx_result_select_schema(const pgx_result* r, int32_t* num_columns, const char** names);
+pgx_status pgx_result_select_counts(const pgx_result* r, int32_t* rows_per_segment);
+pgx_status pgx_result_select_rows(const pgx_result* r, int32_t* seg_index, int32_t* doc_id, int32_t* dict_ids);
 
 /* Per-(segment, leaf) predicate in dictionary-id space, as produced by the caller's PredicateEvaluator:
  * a doc matches iff its dictId d satisfies  (words ? bit d of words : lo <= d <= hi).

@@ -16,6 +16,10 @@ core/query/reduce/BrokerReduceService.java:62-256).  Here:
   + ``reduce`` (query/aggregation/groupby/AggregationGroupByOperatorService.java:93-129), keeps the top N groups per
   function (MIN ascending, others descending: GroupByResultComparator, :405-440) and formats double values with
   ``%1.5f`` and long values with ``toString`` (BrokerReduceService.formatValue, :293-296).
+* Selection requests with ORDER BY: the server's response carries the combined rows under their data schema; the reduce
+  merges all servers' rows with ``SelectionOperatorService.reduceWithOrdering`` (the value comparator over the order
+  columns, offset + size rows kept) and renders them with ``renderSelectionResultsWithOrdering`` / ``getFormattedRow``
+  (query/selection/SelectionOperatorService.java:270-301, SelectionOperatorUtils.java:263-330).
 """
 from __future__ import annotations
 
@@ -136,11 +140,43 @@ def _format(fn: str, v) -> str:
         else java_format_5f(float(v))
 
 
+def java_decimal_format(x: float, min_frac: int, max_frac: int) -> str:
+    """DecimalFormat("#...0.0#...", US).format(double): the shortest decimal representation of the double rounded
+    HALF_EVEN to max_frac fraction digits, trailing zeros cut down to min_frac, no grouping."""
+    if math.isnan(x):
+        return "\ufffd"  # DecimalFormatSymbols.getNaN
+    if math.isinf(x):
+        return "\u221e" if x > 0 else "-\u221e"
+    with decimal.localcontext() as dc:
+        dc.prec = 400  # a double's integer part has up to 309 digits
+        d = decimal.Decimal(repr(float(x))).quantize(decimal.Decimal(1).scaleb(-max_frac),
+                                                     rounding=decimal.ROUND_HALF_EVEN)
+    s = format(abs(d), "f")
+    whole, _, frac = s.partition(".")
+    frac = frac.rstrip("0")
+    frac += "0" * (min_frac - len(frac))
+    neg = math.copysign(1.0, x) < 0
+    return ("-" if neg else "") + whole + ("." + frac if frac else "")
+
+
+def format_selection_value(data_type: str, v) -> str:
+    """SelectionOperatorUtils.DEFAULT_FORMAT_STRING_MAP (:70-81): INT "##########", LONG "####################", FLOAT
+    "#########0.0####", DOUBLE "###################0.0#########"; STRING values pass as they are (getFormattedRow)."""
+    if data_type == "STRING":
+        return v
+    if data_type in ("INT", "LONG"):
+        return str(int(v))
+    return java_decimal_format(float(v), 1, 5 if data_type == "FLOAT" else 10)
+
+
 @dataclass
 class InstanceResponse:
-    """One server's answer (the DataTable's content): aggregation intermediates, or trimmed group-by maps."""
+    """One server's answer (the DataTable's content): aggregation intermediates, trimmed group-by maps, or the
+    selection rows (typed values in data-schema order, best first) with their (column names, data types)."""
     aggregation: Optional[list] = None
     group_by: Optional[List[Dict[str, object]]] = None
+    selection: Optional[List[list]] = None
+    selection_schema: Optional[tuple] = None
     stats: List[int] = field(default_factory=lambda: [0, 0, 0, 0])
     exceptions: Dict[int, str] = field(default_factory=dict)  # error code -> message (EXCEPTION_METADATA_KEY)
 
@@ -164,7 +200,10 @@ class ServerQueryExecutor:
         except Exception as e:  # noqa: BLE001 -- surfaced to the broker as a processing exception
             return InstanceResponse(exceptions={QUERY_EXECUTION_ERROR_CODE: str(e)})
         resp = InstanceResponse(stats=blk.stats.as_list())
-        if broker_request.get("group_by"):
+        if broker_request.get("selections"):
+            resp.selection = [list(r) for r in blk.get_selection_result()]
+            resp.selection_schema = blk.get_selection_data_schema()
+        elif broker_request.get("group_by"):
             resp.group_by = blk.trimmed if blk.trimmed is not None else [{} for _ in broker_request["aggregations"]]
         else:
             resp.aggregation = list(blk.get_aggregation_result())
@@ -188,6 +227,13 @@ class AggregationResult:
 
 
 @dataclass
+class SelectionResults:
+    """common/response/broker/SelectionResults.java: the selection columns and the formatted rows."""
+    columns: List[str]
+    results: List[List[str]]
+
+
+@dataclass
 class QueryProcessingException:
     error_code: int
     message: str
@@ -196,6 +242,7 @@ class QueryProcessingException:
 @dataclass
 class BrokerResponseNative:
     aggregation_results: List[AggregationResult] = field(default_factory=list)
+    selection_results: Optional[SelectionResults] = None
     num_docs_scanned: int = 0
     num_entries_scanned_in_filter: int = 0
     num_entries_scanned_post_filter: int = 0
@@ -217,7 +264,7 @@ class BrokerReduceService:
             if isinstance(resp, (bytes, bytearray)):  # a serialized DataTable (pinot_amd/datatable.py)
                 from .datatable import datatable_to_response
                 resp = datatable_to_response(broker_request, bytes(resp))
-            if resp.aggregation is None and resp.group_by is None:  # schema-less: exception metadata only
+            if resp.aggregation is None and resp.group_by is None and resp.selection is None:  # schema-less: exceptions
                 for code, msg in resp.exceptions.items():
                     out.processing_exceptions.append(QueryProcessingException(int(code), msg))
                 continue
@@ -228,7 +275,10 @@ class BrokerReduceService:
             live[server] = resp
         aggs = broker_request["aggregations"]
         try:
-            if broker_request.get("group_by"):
+            if broker_request.get("selections"):
+                if live:
+                    out.selection_results = self._reduce_selection(broker_request, list(live.values()))
+            elif broker_request.get("group_by"):
                 out.aggregation_results = self._reduce_group_by(broker_request, list(live.values()))
             else:
                 for i, a in enumerate(aggs):
@@ -239,6 +289,22 @@ class BrokerReduceService:
         return out
 
     reduceOnDataTable = reduce_on_data_table
+
+    @staticmethod
+    def _reduce_selection(broker_request: dict, responses: List[InstanceResponse]) -> SelectionResults:
+        """SelectionOperatorService.reduceWithOrdering + renderSelectionResultsWithOrdering: the servers' rows merged
+        by the value comparator down to offset + size, the first `offset` dropped, best first; the columns in the
+        request's order ("*": the schema's columns sorted, getSelectionColumns), every value formatted.  Rows equal
+        in every order column keep the order of the responses and of their rows."""
+        sel = broker_request["selections"]
+        if not sel["order_by"]:
+            raise ValueError("selection without ORDER BY is not on this path")
+        names, types = responses[0].selection_schema
+        lists = [[(row, (s, i)) for i, row in enumerate(r.selection)] for s, r in enumerate(responses)]
+        rows = E.merge_selection_rows(lists, types, sel["order_by"], sel["offset"] + sel["size"])[sel["offset"]:]
+        cols = sorted(names) if sel["columns"] == ["*"] else list(sel["columns"])
+        idx = [list(names).index(c) for c in cols]
+        return SelectionResults(cols, [[format_selection_value(types[i], row[i]) for i in idx] for row, _ in rows])
 
     @staticmethod
     def _reduce_group_by(broker_request: dict, responses: List[InstanceResponse]) -> List[AggregationResult]:

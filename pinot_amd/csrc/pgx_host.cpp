@@ -1407,6 +1407,11 @@ void run_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n
   struct Unmark { ~Unmark() { g_prof_mark = nullptr; } } unmark;
   hipStream_t st = (opts && opts->stream) ? reinterpret_cast<hipStream_t>(opts->stream) : ctx->stream;
   const uint32_t xflags = opts ? opts->flags : 0;
+  if (q.select) {  // selection with ORDER BY: planned afresh every time (no plan cache)
+    if (dom) fail(PGX_ERR_UNSUPPORTED, "selection queries across devices");
+    run_select(ctx, q, segs, n, bindings, opts, R, st);
+    return;
+  }
   // plan cache (single-device plans without a caller key domain; only plain plans are ever kept, so a hit is one)
   const bool cache = !dom && plan_cache_on() && n > 0;
   std::vector<uint64_t> uids;
@@ -1698,6 +1703,7 @@ pgx_status pgx_query_set_key_domain(pgx_query* q, int32_t group_col, int32_t typ
                                     const int64_t* ivals, const double* dvals, const char* const* svals) {
   return guarded([&] {
     if (!q) fail(PGX_ERR_INVALID_ARG, "NULL query");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "key domains on a selection query");
     if (group_col < 0 || group_col >= int(q->group_cols.size())) fail(PGX_ERR_INVALID_ARG, "group column index");
     plan_cache_purge(q, nullptr);  // plans decode keys against the domain
     if (num_values < 0 || num_values > INT32_MAX) fail(PGX_ERR_INVALID_ARG, "key domain size");
@@ -1839,6 +1845,7 @@ pgx_status pgx_execute_multi(pgx_ctx* const* ctxs, int32_t nctx, const pgx_query
     if (!q->leaf_col.empty() && !bindings) fail(PGX_ERR_INVALID_ARG, "filter leaves need bindings");
     if (opts && (opts->stream || opts->dense_out || (opts->flags & PGX_X_KEEP_DENSE_ON_DEVICE)))
       fail(PGX_ERR_INVALID_ARG, "pgx_execute_multi takes flags only (each context runs on its own stream)");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_multi on a selection query");
     auto R = std::make_unique<pgx_result>();
     run_multi(ctxs, nctx, *q, segs, n, bindings, opts ? opts->flags : 0, R.get());
     *out = R.release();
@@ -1903,6 +1910,7 @@ pgx_status pgx_result_agg(const pgx_result* r, int32_t fn, double* value, int64_
     if (r) r->ready();
     if (!r) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     if (r->group_by) fail(PGX_ERR_INVALID_ARG, "group-by result");
+    if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
     if (fn < 0 || fn >= r->num_aggs) fail(PGX_ERR_INVALID_ARG, "function index");
     if (value) *value = r->agg_value[fn];
     if (count) *count = r->agg_count[fn];
@@ -1913,6 +1921,7 @@ pgx_status pgx_result_num_groups(const pgx_result* r, int64_t* n) {
   return guarded([&] {
     if (r) r->ready();
     if (!r || !n) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
     *n = r->num_groups;
   });
 }
@@ -1943,6 +1952,7 @@ pgx_status pgx_result_group_mode(const pgx_result* r, int32_t* mode) {
   return guarded([&] {
     if (r) r->ready();
     if (!r || !mode) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
     *mode = r->mode;
   });
 }
@@ -2024,6 +2034,7 @@ pgx_status pgx_result_gather(const pgx_result* r, const int64_t* gi, int64_t n, 
 pgx_status pgx_query_dense_slots(const pgx_query* q, pgx_segment* const* segs, int32_t n, int64_t* slots) {
   return guarded([&] {
     if (!q || !segs || !slots) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
     if (!q->group_cols.empty() && query_is_mv(*q, segs, n)) {  // multi-value group-by: merged by key, never densely
       *slots = -1;
       return;
@@ -2038,6 +2049,7 @@ pgx_status pgx_query_dense_plane_op(const pgx_query* q, pgx_segment* const* segs
                                     int32_t* op) {
   return guarded([&] {
     if (!q || !segs || !op) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
     if (plane == 0) { *op = P_ADD_I64; return; }
     if (plane < 1 || plane > int(q->agg_fn.size())) fail(PGX_ERR_INVALID_ARG, "plane");
     const int fn = q->agg_fn[plane - 1];
@@ -2052,6 +2064,7 @@ pgx_status pgx_result_from_dense(pgx_ctx* ctx, const pgx_query* q, pgx_segment* 
                                  const void* dense_device, const int64_t stats[4], pgx_result** out) {
   return guarded([&] {
     if (!ctx || !q || !segs || !dense_device || !out) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ExecPlan P;
     std::vector<pgx_leaf_binding> none(size_t(n) * q->leaf_col.size(), pgx_leaf_binding{0, -1, nullptr});
@@ -2227,6 +2240,7 @@ pgx_status pgx_execute_timed(pgx_ctx* ctx, const pgx_query* q, pgx_segment* cons
                              pgx_result** out) {
   return guarded([&] {
     if (!ctx || !q || !segs || iters < 1) fail(PGX_ERR_INVALID_ARG, "bad argument");
+    if (q->select) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_timed on a selection query");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = ctx->stream;
     ExecPlan P;

@@ -114,6 +114,15 @@ extern "C" hipError_t pgx_launch_group_pack(const uint64_t* okey, const uint64_t
 extern "C" hipError_t pgx_launch_group_compact(const unsigned long long* tkey, const unsigned long long* tpl,
                                                uint64_t cap, int nplanes, uint64_t* okey, uint64_t* opl, int64_t ocap,
                                                unsigned long long* counter, hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_topk(const pgx::SelItem* items, int nitems, int K, int wgs_per_item,
+                                             uint64_t* cand_key, uint32_t* cand_doc, int32_t* cand_cnt,
+                                             hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_merge(int nitems, int K, int wgs_per_item, const uint64_t* cand_key,
+                                              const uint32_t* cand_doc, const int32_t* cand_cnt, int32_t* out_doc,
+                                              int32_t* out_cnt, hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_gather(const pgx::SelGatherCol* cols, int nitems, int ncols, int K,
+                                               const int32_t* out_doc, const int32_t* out_cnt, int32_t* out_ids,
+                                               hipStream_t stream);
 struct pgx_ctx;
 extern "C" void ctx_unref(pgx_ctx* ctx);
 
@@ -599,6 +608,12 @@ struct pgx_query {
   uint32_t flags = 0;
   std::vector<KeyDomain> key_domain;  // [group column]
   Knobs kn;                           // the PGX_* environment when the query was compiled (read_knobs)
+  // selection with ORDER BY (pgx_select_compile, pgx_select.cpp): the columns as written ("*" = all), the order
+  // columns and their directions, LIMIT offset, size
+  bool select = false;
+  std::vector<std::string> sel_cols, order_cols;
+  std::vector<int> order_asc;
+  int sel_offset = 0, sel_size = 10;
   // global hash-table size the query's last execution needed (run_query starts there instead of at 1M slots and
   // overflowing once more): a start size only, never a result input
   struct Hint {  // an atomic that copies by value (a query is copied for its multi-value part, pgx_mv.cpp)
@@ -719,6 +734,11 @@ struct pgx_result {
     }
   };
   std::unique_ptr<Lazy> lazy;
+  // selection (run_select): the data schema, rows per segment, and the rows segment by segment, best first
+  bool select = false;
+  std::vector<std::string> sel_schema;
+  std::vector<int32_t> sel_counts, sel_seg, sel_doc;
+  std::vector<int32_t> sel_ids;  // [schema column][row]
   std::unique_ptr<AsyncState> async;  // declared last: destroyed (joined) before the fields its thread writes
   void ready() const;                 // waits for an async execution; throws its error
   void materialize();
@@ -1081,6 +1101,9 @@ void run_mv(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, c
             uint32_t xflags, pgx_result* R, hipStream_t st);
 void run_mv_group(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
                   uint32_t xflags, pgx_result* R, hipStream_t st, const Domain* dom = nullptr);
+
+void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
+                const pgx_exec_opts* opts, pgx_result* R, hipStream_t st);  // pgx_select.cpp
 
 void parse_star_tree(pgx_segment& seg);
 void stage_column(pgx_ctx* ctx, pgx_segment* seg, const pgx_column_desc& d, bool device_mem, StagedColumn& c);

@@ -115,6 +115,30 @@ struct MvGroupArgs {
   unsigned long long* ord;     // MINMV / MAXMV per-segment holders: [seg][agg][slot] (ordered encodings)
 };
 
+// Selection with ORDER BY (pgx_select.hip; MSelectionOrderByOperator / SelectionOperatorService): one item per segment.
+// A row's order key is its order columns' dictIds (card - 1 - id for DESC), kbits each, concatenated most-significant
+// first into one u64; rows are ranked by (key, docId) ascending.
+constexpr int kSelMaxOrderCols = 8;
+constexpr int kSelBlock = 256;
+struct SelCol {
+  const uint32_t* fwd;         // packed big-endian fixed-bit forward index
+  int32_t bits;                // bits per stored dictId
+  int32_t kbits;               // bits the column takes in the key: max(1, ceil(log2 card))
+  uint32_t card;
+  int32_t desc;
+};
+struct SelItem {
+  const uint32_t* sel;         // selected docs: bit (d & 31) of word d >> 5 (written by the query kernel)
+  int32_t num_docs;
+  int32_t ncols;
+  SelCol c[kSelMaxOrderCols];
+};
+struct SelGatherCol {          // one schema column of one item (pgx_select_gather)
+  const uint32_t* fwd;
+  int32_t bits;
+  int32_t pad;
+};
+
 // Statistics automaton over one segment's leaf masks (pgx_kernels.hip pgx_fsm_chunks / pgx_fsm_compose).
 struct FsmSeg {
   const uint32_t* lmask;       // leaf l, row r: bit (r & 31) of word [l * words + (r >> 5)]

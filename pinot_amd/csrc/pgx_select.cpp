@@ -1,0 +1,255 @@
+// libpgx: selection queries with ORDER BY -- SELECT cols | * FROM t [WHERE ...] ORDER BY c1 [ASC|DESC], ... LIMIT.
+// Replaces operator/MSelectionOrderByOperator.java over query/selection/SelectionOperatorService.java (a PriorityQueue of
+// offset + size docs per segment under CompositeDocIdValComparator).  The library returns every segment's best rows as
+// (docId, dictIds); the caller merges the segments' lists by value, where MCombineOperator / SelectionOperatorService
+// .mergeWithOrdering sit in the reference: dictIds of different segments do not compare.
+// Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
+#include "pgx_host.h"
+
+namespace pgxh {
+
+// Data schema of a selection (SelectionOperatorUtils.extractDataSchema:223-253): the order columns in ORDER BY order,
+// then the selected columns sorted by name, minus those already present; "*" is the segment's columns, sorted
+// (getSelectionColumns:152-161).
+static std::vector<std::string> select_schema(const pgx_query& q, const pgx_segment* seg0) {
+  std::vector<std::string> cols = q.order_cols;
+  std::vector<std::string> sel = q.sel_cols;
+  if (sel.size() == 1 && sel[0] == "*") {
+    sel.clear();
+    if (seg0) sel = seg0->names;
+  }
+  std::sort(sel.begin(), sel.end());
+  for (const auto& c : sel)
+    if (std::find(cols.begin(), cols.end(), c) == cols.end()) cols.push_back(c);
+  return cols;
+}
+
+void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
+                const pgx_exec_opts* opts, pgx_result* R, hipStream_t st) {
+  const uint32_t xflags = opts ? opts->flags : 0;
+  if (opts && (opts->dense_out || (xflags & PGX_X_KEEP_DENSE_ON_DEVICE)))
+    fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense output");
+  if (!q.kn.jit) fail(PGX_ERR_UNSUPPORTED, "selection queries need the query kernels");
+  if (n < 0 || n > 65535) fail(PGX_ERR_UNSUPPORTED, "selection over more than 65535 segments");
+  const int K = q.sel_offset + q.sel_size;
+  const int no = int(q.order_cols.size());
+  const std::vector<std::string> schema = select_schema(q, n > 0 ? segs[0] : nullptr);
+  const int nc = int(schema.size());
+
+  // per-segment key layout and column views
+  std::vector<SelItem> items(size_t(std::max(n, 0)));
+  std::vector<SelGatherCol> gcols(size_t(std::max(n, 0)) * size_t(nc));
+  for (int s = 0; s < n; ++s) {
+    SelItem& it = items[size_t(s)];
+    it = SelItem{};
+    it.num_docs = segs[s]->total_docs;
+    it.ncols = no;
+    int total_bits = 0;
+    for (int c = 0; c < no; ++c) {
+      const StagedColumn& col = segs[s]->col(q.order_cols[size_t(c)]);
+      if (col.is_mv) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value column " + col.name);
+      SelCol& k = it.c[c];
+      k.fwd = col.fwd;
+      k.bits = col.bits;
+      k.kbits = bits_for(col.card);
+      k.card = uint32_t(std::max(col.card, 1));
+      k.desc = q.order_asc[size_t(c)] ? 0 : 1;
+      total_bits += k.kbits;
+    }
+    if (total_bits > 64) fail(PGX_ERR_UNSUPPORTED, "selection order key wider than 64 bits");
+    for (int c = 0; c < nc; ++c) {
+      const StagedColumn& col = segs[s]->col(schema[size_t(c)]);
+      if (col.is_mv) fail(PGX_ERR_UNSUPPORTED, "selection of multi-value column " + col.name);
+      gcols[size_t(s) * nc + c] = SelGatherCol{col.fwd, col.bits, 0};
+    }
+  }
+
+  R->select = true;
+  R->group_by = false;
+  R->num_aggs = 0;
+  R->sel_schema = schema;
+  R->sel_counts.assign(size_t(std::max(n, 0)), 0);
+  R->sel_seg.clear();
+  R->sel_doc.clear();
+  R->sel_ids.clear();
+  if (n == 0) return;
+
+  // 1. the filter as COUNT(*): statistics and one selection bit per scanned row
+  pgx_query qs = q;
+  qs.select = false;
+  qs.flags |= PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
+  qs.agg_fn.assign(1, PGX_COUNT);
+  qs.agg_col.assign(1, "");
+  qs.group_cols.clear();
+  qs.key_domain.clear();
+  ExecPlan P;
+  P.want_selmask = true;
+  plan_query(ctx, qs, segs, n, bindings, xflags, P);
+  P.sel_off.assign(size_t(n), 0);
+  int64_t words = 0;
+  int max_words = 0;
+  for (int s = 0; s < n; ++s) {
+    P.sel_off[size_t(s)] = words;
+    const int w = (P.ksegs[size_t(s)].num_docs + 31) / 32 + 1;
+    words += w;
+    max_words = std::max(max_words, w);
+  }
+  P.sel_buf = DevBuf(ctx, size_t(std::max<int64_t>(words, 1)) * 4);
+  hip_check(hipMemsetAsync(P.sel_buf.p, 0, size_t(std::max<int64_t>(words, 1)) * 4, st), "selection masks");
+  ExecBuffers B;
+  upload_plan(ctx, P, B, st);
+  plan_jit(ctx, qs, segs, n, P, B);
+  if (P.jit.empty()) {
+    for (int s = 0; s < n; ++s)
+      if (P.ksegs[size_t(s)].num_docs != 0) fail(PGX_ERR_UNSUPPORTED, "selection queries need the query kernels");
+    R->stats[3] = P.total_raw;  // every segment empty: nothing scanned, no rows
+    return;
+  }
+  alloc_outputs(ctx, P, B, nullptr, 0);
+  reset_outputs(P, B, st);
+  launch_scan(P, st);
+
+  // 2. per-segment top K, merge, gather -- on the same stream
+  for (int s = 0; s < n; ++s) {
+    items[size_t(s)].sel = P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)];
+    items[size_t(s)].num_docs = P.ksegs[size_t(s)].num_docs;
+  }
+  // workgroups per segment: at least 4 steps of 256 mask words each, and no more over all segments than stay resident
+  // (8 of 256 threads per CU, fewer when the candidate buffers fill the LDS): the scan hides its load latency with
+  // resident waves, while every further workgroup adds a candidate list of K rows to the merge
+  int cbuf = 1;
+  while (cbuf < K) cbuf <<= 1;
+  cbuf = std::max(512, 2 * cbuf) * 12;
+  const int resident = std::max(1, std::min(8, (160 * 1024) / (cbuf + 512)));
+  int G = std::max(1, (max_words + 4 * kSelBlock - 1) / (4 * kSelBlock));
+  G = std::min(G, std::max(1, resident * ctx->num_cus / n));
+  G = std::min(G, 64);
+  const size_t slots = size_t(n) * size_t(G);
+  const size_t rows = size_t(n) * size_t(K);
+  DevBuf idev(ctx, items.size() * sizeof(SelItem)), gdev(ctx, std::max<size_t>(1, gcols.size()) * sizeof(SelGatherCol));
+  DevBuf ckey(ctx, slots * K * 8), cdoc(ctx, slots * K * 4), ccnt(ctx, slots * 4);
+  DevBuf odoc(ctx, rows * 4), ocnt(ctx, size_t(n) * 4), oids(ctx, std::max<size_t>(1, rows * nc) * 4);
+  hip_check(hipMemcpyAsync(idev.p, items.data(), items.size() * sizeof(SelItem), hipMemcpyHostToDevice, st),
+            "selection items H2D");
+  if (!gcols.empty())
+    hip_check(hipMemcpyAsync(gdev.p, gcols.data(), gcols.size() * sizeof(SelGatherCol), hipMemcpyHostToDevice, st),
+              "selection columns H2D");
+  PGX_LAUNCH(st, "pgx_select_topk",
+             pgx_launch_select_topk(idev.as<SelItem>(), n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(),
+                                    ccnt.as<int32_t>(), st),
+             "selection top-K");
+  PGX_LAUNCH(st, "pgx_select_merge",
+             pgx_launch_select_merge(n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(), ccnt.as<int32_t>(),
+                                     odoc.as<int32_t>(), ocnt.as<int32_t>(), st),
+             "selection merge");
+  PGX_LAUNCH(st, "pgx_select_gather",
+             pgx_launch_select_gather(gdev.as<SelGatherCol>(), n, nc, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+                                      oids.as<int32_t>(), st),
+             "selection gather");
+  const size_t nseg = size_t(n);
+  std::vector<int32_t> hdoc(rows), hcnt(nseg), hids(rows * nc);
+  hip_check(hipMemcpyAsync(hcnt.data(), ocnt.p, hcnt.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+  hip_check(hipMemcpyAsync(hdoc.data(), odoc.p, hdoc.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+  if (!hids.empty())
+    hip_check(hipMemcpyAsync(hids.data(), oids.p, hids.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+  pgx_result Rs;
+  finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream
+
+  // 3. statistics as MSelectionOrderByOperator.getNextBlock reports them; rows compacted segment by segment
+  R->stats[0] = Rs.stats[0];
+  R->stats[1] = Rs.stats[1];
+  R->stats[2] = Rs.stats[0] * nc;
+  R->stats[3] = Rs.stats[3];
+  int64_t total = 0;
+  for (int s = 0; s < n; ++s) {
+    if (hcnt[size_t(s)] < 0 || hcnt[size_t(s)] > K) fail(PGX_ERR_INTERNAL, "selection row count out of range");
+    total += hcnt[size_t(s)];
+  }
+  R->sel_counts = hcnt;
+  R->sel_seg.reserve(size_t(total));
+  R->sel_doc.reserve(size_t(total));
+  R->sel_ids.assign(size_t(total) * nc, 0);
+  int64_t at = 0;
+  for (int s = 0; s < n; ++s)
+    for (int r = 0; r < hcnt[size_t(s)]; ++r, ++at) {
+      R->sel_seg.push_back(s);
+      R->sel_doc.push_back(hdoc[size_t(s) * K + r]);
+      for (int c = 0; c < nc; ++c)
+        R->sel_ids[size_t(c) * size_t(total) + size_t(at)] = hids[(size_t(c) * n + s) * K + r];
+    }
+}
+
+}  // namespace pgxh
+
+extern "C" {
+
+pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* d, pgx_query** out) {
+  return guarded([&] {
+    if (!ctx || !d || !out) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (d->num_columns < 1 || !d->columns) fail(PGX_ERR_INVALID_ARG, "selection without columns");
+    if (d->num_order_by < 0 || d->offset < 0 || d->size < 0) fail(PGX_ERR_INVALID_ARG, "negative count");
+    if (d->num_order_by == 0) fail(PGX_ERR_UNSUPPORTED, "selection without ORDER BY (MSelectionOnlyOperator)");
+    if (d->num_order_by > kSelMaxOrderCols) fail(PGX_ERR_UNSUPPORTED, "more than 8 ORDER BY columns");
+    if (!d->order_by) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    const int64_t rows = int64_t(d->offset) + d->size;
+    if (rows == 0) fail(PGX_ERR_UNSUPPORTED, "selection of 0 rows (LIMIT 0)");
+    if (rows > PGX_SEL_MAX_ROWS) fail(PGX_ERR_UNSUPPORTED, "selection of more than PGX_SEL_MAX_ROWS rows");
+    auto q = std::make_unique<pgx_query>();
+    q->select = true;
+    for (int c = 0; c < d->num_columns; ++c) {
+      if (!d->columns[c] || !*d->columns[c]) fail(PGX_ERR_INVALID_ARG, "empty column name");
+      q->sel_cols.push_back(d->columns[c]);
+    }
+    for (int c = 0; c < d->num_order_by; ++c) {
+      if (!d->order_by[c].column || !*d->order_by[c].column) fail(PGX_ERR_INVALID_ARG, "empty column name");
+      q->order_cols.push_back(d->order_by[c].column);
+      q->order_asc.push_back(d->order_by[c].ascending != 0);
+    }
+    q->sel_offset = d->offset;
+    q->sel_size = d->size;
+    q->filter.assign(d->filter, d->filter + d->num_filter_nodes);
+    for (int l = 0; l < d->num_leaves; ++l) {
+      q->leaf_col.push_back(d->leaves[l].column);
+      q->leaf_kind.push_back(d->leaves[l].kind);
+    }
+    q->agg_fn.assign(1, PGX_COUNT);  // what the filter runs as (run_select); never reported
+    q->agg_col.assign(1, "");
+    q->flags = d->flags | PGX_Q_NO_STAR_TREE;
+    q->kn = read_knobs();
+    *out = q.release();
+  });
+}
+
+static const pgx_result& select_result(const pgx_result* r) {
+  if (r) r->ready();
+  if (!r || !r->select) fail(PGX_ERR_INVALID_ARG, "not a selection result");
+  return *r;
+}
+
+pgx_status pgx_result_select_schema(const pgx_result* r, int32_t* num_columns, const char** names) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    if (num_columns) *num_columns = int32_t(S.sel_schema.size());
+    if (names)
+      for (size_t c = 0; c < S.sel_schema.size(); ++c) names[c] = S.sel_schema[c].c_str();  // owned by the result
+  });
+}
+
+pgx_status pgx_result_select_counts(const pgx_result* r, int32_t* rows_per_segment) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    if (!rows_per_segment) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    std::copy(S.sel_counts.begin(), S.sel_counts.end(), rows_per_segment);
+  });
+}
+
+pgx_status pgx_result_select_rows(const pgx_result* r, int32_t* seg_index, int32_t* doc_id, int32_t* dict_ids) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    if (seg_index) std::copy(S.sel_seg.begin(), S.sel_seg.end(), seg_index);
+    if (doc_id) std::copy(S.sel_doc.begin(), S.sel_doc.end(), doc_id);
+    if (dict_ids) std::copy(S.sel_ids.begin(), S.sel_ids.end(), dict_ids);
+  });
+}
+
+}  // extern "C"

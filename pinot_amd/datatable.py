@@ -22,7 +22,10 @@ writes and reads exactly that layout, so a GPU server is wire-compatible with a 
 The server side mirrors getAggregationResultDataTable (one row, one column per function: LONG count_star, DOUBLE
 sum / min / max, OBJECT for the rest) and getAggregationGroupByResultDataTable (one row per function: STRING function
 name, OBJECT HashMap<group string, intermediate>), then attachMetadataToDataTable (numDocsScanned,
-numEntriesScannedInFilter, numEntriesScannedPostFilter, totalDocs, "Exception<code>" entries).  Java HashMap iteration
+numEntriesScannedInFilter, numEntriesScannedPostFilter, totalDocs, "Exception<code>" entries).  A selection response is
+the rows under their data schema (SelectionOperatorUtils.getDataTableFromRowSet, query/selection/SelectionOperatorUtils
+.java: one INT / LONG / FLOAT / DOUBLE / STRING cell per single-value column); no reference fixture pins these bytes,
+they are checked by round trip only.  Java HashMap iteration
 order (the order the reference writes map entries and metadata) is reproduced for String keys: buckets of
 (h ^ h >>> 16) & (capacity - 1) over String.hashCode at the capacity a default HashMap grows to, entries of one bucket
 in insertion order.  IntOpenHashSet's order is fastutil's internal table order in the reference and ascending here;
@@ -421,6 +424,10 @@ def response_to_datatable(broker_request: dict, resp) -> bytes:
         dt = DataTable([function_name(a) for a in aggs], types)
         dt.rows.append([int(v) if t == "LONG" else (float(v) if t == "DOUBLE" else _to_object(a["fn"], v))
                         for a, t, v in zip(aggs, types, resp.aggregation)])
+    elif getattr(resp, "selection", None) is not None:
+        names, types = resp.selection_schema
+        dt = DataTable(list(names), list(types))
+        dt.rows = [list(row) for row in resp.selection]
     elif resp.group_by is not None:
         dt = DataTable(["functionName", "GroupByResultMap"], ["STRING", "OBJECT"])
         for a, m in zip(aggs, resp.group_by):
@@ -449,6 +456,10 @@ def datatable_to_response(broker_request: dict, b: bytes):
     resp.stats = [int(dt.metadata.get(k, 0)) for k in (NUM_DOCS_SCANNED, NUM_ENTRIES_SCANNED_IN_FILTER,
                                                        NUM_ENTRIES_SCANNED_POST_FILTER, TOTAL_DOCS)]
     if not dt.columns:
+        return resp
+    if broker_request.get("selections"):
+        resp.selection = [list(row) for row in dt.rows]
+        resp.selection_schema = (list(dt.columns), list(dt.types))
         return resp
     aggs = broker_request["aggregations"]
     if dt.columns == ["functionName", "GroupByResultMap"]:

@@ -427,9 +427,20 @@ class IntermediateResultsBlock:
     aggregation_group_by_result: Optional[AggregationGroupByResult] = None
     trimmed: Optional[List[Dict[str, object]]] = None  # combine output after trimToSize (one map per function)
     stats: ExecutionStatistics = field(default_factory=ExecutionStatistics)
+    # selection (MSelectionOrderByOperator): rows in data-schema order with typed values, best first; the schema as
+    # (column names, data types); per row its (segment index, docId)
+    selection_result: Optional[List[list]] = None
+    selection_data_schema: Optional[tuple] = None
+    selection_row_ids: Optional[List[tuple]] = None
 
     def get_aggregation_result(self):
         return self.aggregation_result
+
+    def get_selection_result(self):
+        return self.selection_result
+
+    def get_selection_data_schema(self):
+        return self.selection_data_schema
 
     def get_aggregation_group_by_result(self):
         return self.aggregation_group_by_result
@@ -580,6 +591,110 @@ class _Query:
             self.close()
         except Exception:
             pass
+
+
+class _SelectQuery(_Query):
+    """A compiled selection query (pgx_select_compile) for one broker request with "selections"."""
+
+    def __init__(self, ctx: Context, request: dict):
+        self.ctx = ctx
+        self.request = request
+        sel = request["selections"]
+        self.fns, self.group_cols, self.domains = [], [], {}
+        self.order_by = list(sel["order_by"])
+        self.offset, self.size = int(sel["offset"]), int(sel["size"])
+        cols = [c.encode() for c in sel["columns"]]
+        carr = (C.c_char_p * max(1, len(cols)))(*cols)
+        oarr = (N.OrderBy * max(1, len(self.order_by)))()
+        okeep = [o["column"].encode() for o in self.order_by]
+        for i, o in enumerate(self.order_by):
+            oarr[i].column = okeep[i]
+            oarr[i].ascending = 1 if o["asc"] else 0
+        nodes, leaves = _flatten_filter(request.get("filter"))
+        self.leaves = leaves
+        narr = (N.FilterNode * max(1, len(nodes)))()
+        for i, (op, arg) in enumerate(nodes):
+            narr[i].op, narr[i].arg = op, arg
+        larr = (N.Leaf * max(1, len(leaves)))()
+        lkeep = [lf["column"].encode() for lf in leaves]
+        for i, lf in enumerate(leaves):
+            larr[i].column = lkeep[i]
+            larr[i].kind = N.PGX_PRED[lf["op"]]
+        sd = N.SelectDesc(len(cols), carr, len(self.order_by), oarr, self.offset, self.size, len(nodes), narr,
+                          len(leaves), larr, 0)
+        self._keep = [cols, carr, oarr, okeep, narr, larr, lkeep]
+        h = C.c_void_p()
+        N.check(N.lib().pgx_select_compile(ctx.handle, C.byref(sd), C.byref(h)))
+        self.handle = h
+
+
+def _typed_value(col: _ColInfo, dict_id: int):
+    """The dictionary value as SelectionFetcher reads it: Integer / Long -> int, Float (kept exactly) / Double ->
+    float, String -> str."""
+    dt = col.meta.data_type
+    v = col.values[dict_id]
+    if dt == "STRING":
+        return str(v)
+    if dt in ("INT", "LONG"):
+        return int(v)
+    return float(np.float32(v)) if dt == "FLOAT" else float(v)
+
+
+def _java_compare(data_type: str, a, b) -> int:
+    """Integer / Long / Float / Double.compareTo and String.compareTo (UTF-16 code units): -0.0 < 0.0, NaN above all."""
+    if data_type == "STRING":
+        a, b = a.encode("utf-16-be"), b.encode("utf-16-be")
+    elif data_type in ("FLOAT", "DOUBLE"):
+        a = (1, 0.0, 0.0) if a != a else (0, a, math.copysign(1.0, a))
+        b = (1, 0.0, 0.0) if b != b else (0, b, math.copysign(1.0, b))
+    return -1 if a < b else (1 if a > b else 0)
+
+
+def merge_selection_rows(lists, types, order_by, limit):
+    """The value merge of MCombineOperator over the segments' lists (SelectionOperatorService.mergeWithOrdering under
+    getComparator: the first len(order_by) schema columns, each ascending or descending), down to `limit` rows, best
+    first.  lists: per segment (or server) a list of (row values in schema order, (segment index, docId)); ties of
+    the whole key go by (segment index, docId) -- this project's tie rule, where the reference's PriorityQueue keeps
+    whichever its heap order leaves."""
+    import functools
+
+    def cmp(x, y):
+        for i, o in enumerate(order_by):
+            r = _java_compare(types[i], x[0][i], y[0][i])
+            if r:
+                return r if o["asc"] else -r
+        return -1 if x[1] < y[1] else (1 if x[1] > y[1] else 0)
+
+    rows = [r for lst in lists for r in lst]
+    rows.sort(key=functools.cmp_to_key(cmp))
+    return rows[:limit]
+
+
+def decode_selection(q: _SelectQuery, r, segments: Sequence[IndexSegment]):
+    """A selection result as (stats, column names, data types, per-segment lists of (typed row, (segment, docId)))."""
+    L = N.lib()
+    st = (C.c_int64 * 4)()
+    N.check(L.pgx_result_stats(r, st))
+    nc = C.c_int32()
+    N.check(L.pgx_result_select_schema(r, C.byref(nc), None))
+    names = (C.c_char_p * max(1, nc.value))()
+    N.check(L.pgx_result_select_schema(r, C.byref(nc), names))
+    cols = [names[i].decode() for i in range(nc.value)]
+    counts = np.zeros(max(1, len(segments)), np.int32)
+    N.check(L.pgx_result_select_counts(r, counts.ctypes.data))
+    total = int(counts[:len(segments)].sum())
+    seg = np.zeros(max(1, total), np.int32)
+    doc = np.zeros(max(1, total), np.int32)
+    ids = np.zeros(max(1, total * len(cols)), np.int32)
+    N.check(L.pgx_result_select_rows(r, seg.ctypes.data, doc.ctypes.data, ids.ctypes.data))
+    ids = ids[:total * len(cols)].reshape(len(cols), total)
+    types = [segments[0].column(c).meta.data_type for c in cols] if segments else []
+    lists = [[] for _ in segments]
+    for j in range(total):
+        s = int(seg[j])
+        infos = [segments[s].column(c) for c in cols]
+        lists[s].append(([_typed_value(ci, int(ids[c, j])) for c, ci in enumerate(infos)], (s, int(doc[j]))))
+    return ExecutionStatistics(*list(st)), cols, types, lists
 
 
 class _Bindings:
@@ -916,6 +1031,31 @@ class AggregationGroupByOperator(_GpuOperator):
     pass
 
 
+class MSelectionOrderByOperator(_GpuOperator):
+    """operator/MSelectionOrderByOperator.java over the library's per-segment top rows; with combine, MCombineOperator's
+    merge of the segments' lists by value down to offset + size rows."""
+
+    def next_block(self):
+        if self._done:
+            return None
+        q = _SelectQuery(self.ctx, self.request)
+        try:
+            r = q.execute(self.segments)
+            try:
+                stats, cols, types, lists = decode_selection(q, r, self.segments)
+            finally:
+                N.lib().pgx_result_release(r)
+        finally:
+            q.close()
+        rows = merge_selection_rows(lists, types, q.order_by, q.offset + q.size)
+        self._stats = stats
+        self._done = True
+        return IntermediateResultsBlock(stats=stats, selection_result=[r[0] for r in rows],
+                                        selection_data_schema=(cols, types), selection_row_ids=[r[1] for r in rows])
+
+    nextBlock = next_block
+
+
 class PlanNode:
     def __init__(self, op_factory):
         self._f = op_factory
@@ -937,18 +1077,23 @@ class Plan:
 
 
 class InstancePlanMakerImplV2:
-    """plan/maker/InstancePlanMakerImplV2.java:72-109 for aggregation and aggregation-group-by queries."""
+    """plan/maker/InstancePlanMakerImplV2.java:72-109 for aggregation, aggregation-group-by and selection queries."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
 
+    @staticmethod
+    def _operator(broker_request: dict):
+        if broker_request.get("selections"):  # ORDER BY or not: the library refuses what it does not run
+            return MSelectionOrderByOperator
+        return AggregationGroupByOperator if broker_request.get("group_by") else AggregationOperator
+
     def make_inner_segment_plan(self, segment: IndexSegment, broker_request: dict) -> PlanNode:
-        cls = AggregationGroupByOperator if broker_request.get("group_by") else AggregationOperator
+        cls = self._operator(broker_request)
         return PlanNode(lambda: cls(self.ctx, broker_request, [segment], combine=False))
 
     def make_inter_segment_plan(self, segments: Sequence[IndexSegment], broker_request: dict) -> Plan:
-        cls = AggregationGroupByOperator if broker_request.get("group_by") else AggregationOperator
-        return Plan(cls(self.ctx, broker_request, segments, combine=True))
+        return Plan(self._operator(broker_request)(self.ctx, broker_request, segments, combine=True))
 
     makeInnerSegmentPlan = make_inner_segment_plan
     makeInterSegmentPlan = make_inter_segment_plan

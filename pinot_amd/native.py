@@ -70,6 +70,20 @@ class QueryDesc(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class OrderBy(C.Structure):
+    _fields_ = [("column", C.c_char_p), ("ascending", C.c_int32)]
+
+
+class SelectDesc(C.Structure):
+    _fields_ = [("num_columns", C.c_int32), ("columns", C.POINTER(C.c_char_p)), ("num_order_by", C.c_int32),
+                ("order_by", C.POINTER(OrderBy)), ("offset", C.c_int32), ("size", C.c_int32),
+                ("num_filter_nodes", C.c_int32), ("filter", C.POINTER(FilterNode)), ("num_leaves", C.c_int32),
+                ("leaves", C.POINTER(Leaf)), ("flags", C.c_uint32)]
+
+
+PGX_SEL_MAX_ROWS = 2048
+
+
 class LeafBinding(C.Structure):
     _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("words", C.POINTER(C.c_uint32))]
 
@@ -109,6 +123,10 @@ EXPORTS = {
     "pgx_segment_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pgx_query_compile": (C.c_int, [C.c_void_p, C.POINTER(QueryDesc), C.POINTER(C.c_void_p)]),
     "pgx_query_release": (C.c_int, [C.c_void_p]),
+    "pgx_select_compile": (C.c_int, [C.c_void_p, C.POINTER(SelectDesc), C.POINTER(C.c_void_p)]),
+    "pgx_result_select_schema": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
+    "pgx_result_select_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pgx_result_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgx_query_set_key_domain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "pgx_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(LeafBinding),

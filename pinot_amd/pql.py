@@ -15,6 +15,12 @@ The output is a plain dict (the "query spec") shared by the product path and the
    "group_by": {"columns": [...], "top_n": 10} | None,
    "filter": None | {"op": "AND"|"OR", "children": [...]}
                    | {"op": "EQ"|"NEQ"|"IN"|"NOT_IN"|"RANGE", "column": c, "values": [str, ...]}}
+
+Selection requests (PQL2.g4 outputColumns without a function call; SelectAstNode.java:97-134) compile to the same dict
+with an empty aggregation list and
+   "selections": {"columns": ["*"] | [...], "order_by": [{"column": c, "asc": bool}, ...], "offset": 0, "size": 10}
+(ORDER BY expr [ASC|DESC], ascending by default, OrderByExpressionAstNode; LIMIT n, or LIMIT offset, n as
+Pql2AstListener.enterLimit reads it; size 10 and offset 0 by default; the clauses in any order, each at most once).
 """
 import re
 
@@ -137,9 +143,72 @@ class _P:
         raise PqlError("unsupported predicate near %r" % (v,))
 
 
+def _int_literal(p):
+    v = p.literal()
+    if not re.fullmatch(r"\d+", v):
+        raise PqlError("expected an integer, got %r" % (v,))
+    return int(v)
+
+
+def _compile_selection(p):
+    """SELECT cols | * FROM t [WHERE ...] [ORDER BY ...] [LIMIT ...], the parser standing behind SELECT."""
+    if p.peek() == ("op", "*"):
+        p.take()
+        cols = ["*"]
+    else:
+        cols = [p.take("id")]
+        while p.peek() == ("op", ","):
+            p.take()
+            cols.append(p.take("id"))
+    p.take("id", "FROM")
+    table = p.take("id")
+    filt, order, limit = None, None, None
+    seen = set()
+
+    def once(clause):
+        if clause in seen:
+            raise PqlError("repeated %s clause" % clause)
+        seen.add(clause)
+
+    while p.peek()[0] is not None:
+        if p.kw("WHERE"):
+            once("WHERE")
+            p.take()
+            filt = p.predicate()
+        elif p.kw("ORDER"):
+            once("ORDER BY")
+            p.take()
+            p.take("id", "BY")
+            order = []
+            while True:
+                col, asc = p.take("id"), True
+                if p.kw("ASC") or p.kw("DESC"):
+                    asc = p.take().upper() == "ASC"
+                order.append({"column": col, "asc": asc})
+                if p.peek() != ("op", ","):
+                    break
+                p.take()
+        elif p.kw("LIMIT"):
+            once("LIMIT")
+            p.take()
+            a = _int_literal(p)
+            if p.peek() == ("op", ","):
+                p.take()
+                limit = (a, _int_literal(p))
+            else:
+                limit = (0, a)
+        else:
+            raise PqlError("unexpected token %r" % (p.peek()[1],))
+    offset, size = limit if limit is not None else (0, 10)
+    return {"table": table, "aggregations": [], "group_by": None, "filter": filt,
+            "selections": {"columns": cols, "order_by": order or [], "offset": offset, "size": size}}
+
+
 def compile(pql: str) -> dict:  # noqa: A001 - mirrors Pql2Compiler.compileToBrokerRequest
     p = _P(_tokenize(pql))
     p.take("id", "SELECT")
+    if p.peek() == ("op", "*") or (p.peek()[0] == "id" and p.peek(1) != ("op", "(")):
+        return _compile_selection(p)
     aggs = []
     while True:
         fn = p.take("id").lower()
