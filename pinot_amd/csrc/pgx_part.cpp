@@ -573,7 +573,7 @@ void pgx_result::materialize() {
 
 // Combine trim of a device-resident result (pgx_trim.hip): indices of the `size` best groups for function fn, best
 // first (ties in index order).  The first call selects for EVERY function of the result in one set of launches (one
-// range pass, <= 8 histogram passes, one select, all functions side by side) and keeps the selections.
+// range pass, <= 6 histogram passes of 11-bit digits, one select, all functions side by side) and keeps the selections.
 const std::vector<int64_t>& pgx_result::device_trim(int fn, int64_t size) {
   Lazy& L = *lazy;
   const int nf = int(L.agg_kind.size());

@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(256) pgx_group_gather(const uint64_t* __restri
 }  // namespace pgx
 
 // Host launchers (pgx_part.cpp device_trim).  The nf state blocks are prepared by the caller: k = groups wanted, kmin = ~0,
-// everything else zero.  kinds[f]: TrimKind of function slot f.  At most 8 histogram passes (8-bit digits); passes after
+// everything else zero.  kinds[f]: TrimKind of function slot f.  At most 6 histogram passes (11-bit digits); passes after
 // a function's threshold is complete return at once.
 extern "C" hipError_t pgx_launch_trim(const uint64_t* oplane, int64_t ocap, int64_t n, const int* kinds,
                                       const int* planes, int nf,
