@@ -40,7 +40,7 @@ extern "C" {
 #define PGX_ABI_VERSION 8  /* 7: pgx_mutable_* (realtime segments in place); 8: pgx_result_record_words, records of
                               * every device-resident layout (several value columns, f64 sums); pgx_select_compile and
                               * pgx_result_select_* were added under 8: new entry points only, no existing struct or
-                              * call changed */
+                              * call changed; likewise PGX_DISTINCTCOUNTHLL, pgx_result_hll and pgx_hll_codes */
 
 typedef enum {
   PGX_OK = 0,
@@ -56,8 +56,12 @@ typedef enum { PGX_INT = 0, PGX_LONG = 1, PGX_FLOAT = 2, PGX_DOUBLE = 3, PGX_STR
 
 /* The *MV functions aggregate every value of a multi-value column in the selected docs
  * (operator/aggregation/function/{Count,Sum,Min,Max,Avg}MVAggregationFunction.java); aggregation-only queries. */
+/* PGX_DISTINCTCOUNTHLL (operator/aggregation/function/DistinctCountHLLAggregationFunction.java): a single-value
+ * column of any of the five data types; its intermediate is 256 HyperLogLog registers per result (per group), read
+ * with pgx_result_hll (below, "DISTINCTCOUNTHLL"). */
 typedef enum { PGX_COUNT = 0, PGX_SUM = 1, PGX_MIN = 2, PGX_MAX = 3, PGX_AVG = 4,
-               PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9 } pgx_agg_fn;
+               PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9,
+               PGX_DISTINCTCOUNTHLL = 10 } pgx_agg_fn;
 
 /* Predicate kinds (common/Predicate.java Type); they select the physical filter operator exactly as
  * plan/FilterPlanNode.java:118-132 does and drive the numEntriesScannedInFilter statistic. */
@@ -360,6 +364,36 @@ pgx_status pgx_result_trim(const pgx_result* r, int32_t fn_index, int64_t* group
  * only these n groups.  Any output may be NULL. */
 pgx_status pgx_result_gather(const pgx_result* r, const int64_t* group_index, int64_t n, int32_t* seg_index,
                              int32_t* dict_id, double* value, int64_t* count);
+
+/* ---- DISTINCTCOUNTHLL ---------------------------------------------------------------------------
+ * A query may mix PGX_DISTINCTCOUNTHLL functions (also several over one column) with the standard single-value
+ * functions in any order, aggregation-only or under GROUP BY; results keep the request's function order.  The filter,
+ * the standard functions and the groups run as they do without the HLL functions (never from a star tree: every raw
+ * row is offered), and numEntriesScannedPostFilter counts each HLL column among the projected columns once.
+ * pgx_result_hll writes num_groups x 256 bytes: register j of group first_group + i at registers[i * 256 + j], the
+ * groups in the order of pgx_result_group_keys / _values; an aggregation-only result has exactly one group
+ * (first_group 0, num_groups 1).  The registers are those of stream-lib's HyperLogLog(log2m = 8) after
+ * offer((int) hashCode(value)) of every selected doc's value: exact, whatever the order.  PGX_ERR_INVALID_ARG: agg_index
+ * is not a PGX_DISTINCTCOUNTHLL function, or the range lies outside the result.
+ * Numeric accessors on an HLL function index: those that address ONE function -- pgx_result_agg,
+ * pgx_result_group_values, pgx_result_trim -- return PGX_ERR_INVALID_ARG; pgx_result_gather, which returns every
+ * function at once, puts value 0 and count 0 there.
+ * PGX_ERR_UNSUPPORTED (the caller falls back): under GROUP BY a key space that is not dense (hash or partitioned keys,
+ * PGX_X_FORCE_HASH) or has more than PGX_HLL_MAX_GROUP_SLOTS slots (the product of the group columns' cardinalities
+ * over the executed segments); a multi-value column, group column or function in the same query; pgx_execute_multi;
+ * key domains; a caller's dense table (dense_out, PGX_X_KEEP_DENSE_ON_DEVICE, pgx_query_dense_slots and the other
+ * dense-table calls); pgx_execute_timed; PGX_JIT=0. */
+#define PGX_HLL_MAX_GROUP_SLOTS 65536
+pgx_status pgx_result_hll(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
+                          uint8_t* registers);
+/* Host only, no device needed: codes[i] = (register << 8) | rank of offer((int) hashCode(value i)), the per-dictId
+ * table the kernels gather from.  values: int32 / int64 / float / double per data_type, or for PGX_STRING the values'
+ * UTF-8 bytes back to back with n + 1 offsets (string_offsets, else NULL).  hashCode is the boxed Java value's:
+ * Integer the value, Long (int)(v ^ v >>> 32), Float floatToIntBits, Double (int)(bits ^ bits >>> 32), String
+ * 31 * h + unit over the UTF-16 code units (surrogate pairs for supplementary code points); then MurmurHash.hashLong
+ * x, register x >>> 24, rank numberOfLeadingZeros((x << 8) | 0x81) + 1 (1..25). */
+pgx_status pgx_hll_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
+                         uint16_t* codes);
 
 /* Dense-table layout for PGX_X_KEEP_DENSE_ON_DEVICE (multi-GPU RCCL merge):
  * slots = product of group cardinalities; buffer = (1 + num_aggs) planes of slots x 8 bytes.

@@ -1,0 +1,375 @@
+// libpgx: DISTINCTCOUNTHLL -- the per-dictId code tables, the runner and the register accessor.
+// DistinctCountHLLAggregationFunction (operator/aggregation/function/DistinctCountHLLAggregationFunction.java:51-92)
+// offers (int) hashCode of every selected doc's value to a stream-lib HyperLogLog(log2m = 8); the executor hands it
+// DataFetcher.getSVHashCodeArray (common/DataFetcher.java:242-248: dictionary.get(dictId).hashCode()).  The kernels
+// are in pgx_hll.hip.  Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
+#include "pgx_host.h"
+
+namespace pgxh {
+
+// MurmurHash.hashLong (stream-lib 2.7.0: MurmurHash2 over the low, then the high half), in Java int arithmetic.
+static uint32_t murmur_hash_long(int64_t v) {
+  const uint32_t m = 0x5BD1E995u;
+  uint32_t k = uint32_t(uint64_t(v)) * m;
+  k ^= k >> 24;
+  uint32_t h = k * m;
+  k = uint32_t(uint64_t(v) >> 32) * m;
+  k ^= k >> 24;
+  h *= m;
+  h ^= k * m;
+  h ^= h >> 13;
+  h *= m;
+  h ^= h >> 15;
+  return h;
+}
+
+// HyperLogLog.offer(Integer) -> offerHashed: register x >>> 24, rank nlz((x << 8) | 0x81) + 1 (1..25).
+static uint16_t hll_code(int32_t hash_code) {
+  const uint32_t x = murmur_hash_long(int64_t(hash_code));
+  const uint32_t w = (x << 8) | 0x81u;
+  return uint16_t(((x >> 24) << 8) | uint32_t(__builtin_clz(w) + 1));
+}
+
+static int32_t hash_long(int64_t v) { return int32_t(uint32_t(uint64_t(v) ^ (uint64_t(v) >> 32))); }
+static int32_t hash_float(float f) {  // Float.hashCode: floatToIntBits (NaN canonical)
+  if (f != f) return 0x7FC00000;
+  int32_t b;
+  std::memcpy(&b, &f, 4);
+  return b;
+}
+static int32_t hash_double(double d) {  // Double.hashCode: (int)(bits ^ bits >>> 32) of doubleToLongBits
+  uint64_t b = 0x7FF8000000000000ull;
+  if (d == d) std::memcpy(&b, &d, 8);
+  return int32_t(uint32_t(b ^ (b >> 32)));
+}
+// String.hashCode over the UTF-16 code units of a UTF-8 string (a malformed byte decodes to U+FFFD)
+static int32_t hash_utf8(const uint8_t* s, size_t n) {
+  uint32_t h = 0;
+  for (size_t i = 0; i < n;) {
+    uint32_t cp = 0xFFFDu;
+    const uint8_t b = s[i];
+    int more = b < 0x80 ? 0 : (b >> 5) == 6 ? 1 : (b >> 4) == 14 ? 2 : (b >> 3) == 30 ? 3 : -1;
+    if (more >= 0 && i + size_t(more) < n) {
+      uint32_t x = more == 0 ? b : more == 1 ? (b & 0x1Fu) : more == 2 ? (b & 0x0Fu) : (b & 0x07u);
+      bool ok = true;
+      for (int k = 1; k <= more; ++k) {
+        ok = ok && (s[i + k] >> 6) == 2;
+        x = (x << 6) | (s[i + k] & 0x3Fu);
+      }
+      if (ok && x <= 0x10FFFFu) {
+        cp = x;
+        i += size_t(more);
+      }
+    }
+    ++i;
+    if (cp >= 0x10000u) {  // a surrogate pair
+      cp -= 0x10000u;
+      h = 31u * h + (0xD800u + (cp >> 10));
+      h = 31u * h + (0xDC00u + (cp & 0x3FFu));
+    } else {
+      h = 31u * h + cp;
+    }
+  }
+  return int32_t(h);
+}
+
+// The column's code table in HBM, built on the first query that names it.  Numeric dictionaries share it through
+// their SharedDict (keyed by type and content); a STRING column keeps its own.  Both belong to one staged dictionary:
+// a realtime snapshot stages its (grown) dictionaries afresh and so never sees an earlier table.
+static const uint16_t* hll_code_table(pgx_ctx* ctx, const StagedColumn& c) {
+  std::lock_guard<std::mutex> g(ctx->dict_mu);
+  DevBuf& buf = c.shared ? c.shared->hll_codes : c.hll_codes;
+  if (buf.p) return buf.as<uint16_t>();
+  std::vector<uint16_t> codes(size_t(std::max(c.card, 1)), 0);
+  for (int i = 0; i < c.card; ++i) {
+    int32_t h;
+    switch (c.data_type) {
+      case PGX_INT: h = int32_t(c.ivals[size_t(i)]); break;
+      case PGX_LONG: h = hash_long(c.ivals[size_t(i)]); break;
+      case PGX_FLOAT: h = hash_float(float(c.dvals[size_t(i)])); break;
+      case PGX_DOUBLE: h = hash_double(c.dvals[size_t(i)]); break;
+      default:
+        h = hash_utf8(reinterpret_cast<const uint8_t*>(c.svals[size_t(i)].data()), c.svals[size_t(i)].size());
+        break;
+    }
+    codes[size_t(i)] = hll_code(h);
+  }
+  DevBuf b(ctx, codes.size() * 2);
+  hip_check(hipMemcpy(b.p, codes.data(), codes.size() * 2, hipMemcpyHostToDevice), "HLL codes H2D");
+  buf = std::move(b);
+  return buf.as<uint16_t>();
+}
+
+// workgroups per item: at least 4 steps of 256 mask words each, and no more over all items than stay resident
+static int hll_wgs(const pgx_ctx* ctx, int max_words, size_t nitems) {
+  int G = std::max(1, (max_words + 4 * kHllBlock - 1) / (4 * kHllBlock));
+  G = std::min(G, std::max(1, int(size_t(8 * ctx->num_cus) / std::max<size_t>(1, nitems))));
+  return std::min(G, 64);
+}
+
+// A query with DISTINCTCOUNTHLL functions: the rest of it (its filter, its standard functions or COUNT(*) alone, its
+// GROUP BY) runs through the query kernels, which also write every scanned row's selection bit; pgx_hll_offer
+// [_group] then offers every selected row's code.  Planned afresh every time (no plan cache).
+void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
+             const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom) {
+  const uint32_t xflags = opts ? opts->flags : 0;
+  if (dom) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL across devices");
+  if (opts && (opts->dense_out || (xflags & PGX_X_KEEP_DENSE_ON_DEVICE)))
+    fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL into a caller's dense table");
+  if (!q.kn.jit) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL needs the query kernels");
+  for (const auto& d : q.key_domain)
+    if (d.set) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL with a key domain");
+  if (n < 1) fail(PGX_ERR_INVALID_ARG, "no segments");
+  const int na = int(q.agg_fn.size()), ng = int(q.group_cols.size());
+  pgx_query qs = q;
+  qs.flags |= PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
+  qs.agg_fn.clear();
+  qs.agg_col.clear();
+  std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1);
+  std::vector<std::string> hcols;
+  for (int a = 0; a < na; ++a) {
+    const int f = q.agg_fn[size_t(a)];
+    if (f == PGX_DISTINCTCOUNTHLL) {
+      const std::string& c = q.agg_col[size_t(a)];
+      for (int s = 0; s < n; ++s)
+        if (segs[s]->col(c).is_mv) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on multi-value column " + c);
+      auto it = std::find(hcols.begin(), hcols.end(), c);
+      hll_pos[size_t(a)] = int(it - hcols.begin());
+      if (it == hcols.end()) hcols.push_back(c);
+    } else {
+      if (f >= PGX_COUNTMV) fail(PGX_ERR_UNSUPPORTED, "multi-value functions together with DISTINCTCOUNTHLL");
+      sv_pos[size_t(a)] = int(qs.agg_fn.size());
+      qs.agg_fn.push_back(f);
+      qs.agg_col.push_back(q.agg_col[size_t(a)]);
+    }
+  }
+  for (const auto& g : q.group_cols)
+    for (int s = 0; s < n; ++s)
+      if (segs[s]->col(g).is_mv) fail(PGX_ERR_UNSUPPORTED, "multi-value group column together with DISTINCTCOUNTHLL");
+  if (qs.agg_fn.empty()) {
+    qs.agg_fn.push_back(PGX_COUNT);
+    qs.agg_col.push_back("");
+  }
+  const size_t nh = hcols.size();
+
+  // 1. the rest of the query, with selection bits
+  ExecPlan P;
+  P.want_selmask = true;
+  plan_query(ctx, qs, segs, n, bindings, xflags, P);
+  const KQuery& K = P.kq;
+  const bool dense = K.group_mode == G_DENSE_LDS || K.group_mode == G_DENSE_GLOBAL;
+  if (ng > 0 && (!dense || P.use_part || P.dense_slots > uint64_t(PGX_HLL_MAX_GROUP_SLOTS)))
+    fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: dense key spaces of up to PGX_HLL_MAX_GROUP_SLOTS only");
+  P.sel_off.assign(size_t(n), 0);
+  int64_t words = 0;
+  int max_words = 0;
+  for (int s = 0; s < n; ++s) {
+    P.sel_off[size_t(s)] = words;
+    const int w = (P.ksegs[size_t(s)].num_docs + 31) / 32 + 1;
+    words += w;
+    max_words = std::max(max_words, w);
+  }
+  P.sel_buf = DevBuf(ctx, size_t(std::max<int64_t>(words, 1)) * 4);
+  hip_check(hipMemsetAsync(P.sel_buf.p, 0, size_t(std::max<int64_t>(words, 1)) * 4, st), "selection masks");
+  ExecBuffers B;
+  upload_plan(ctx, P, B, st);
+  plan_jit(ctx, qs, segs, n, P, B);
+  bool scanned = !(P.jit.empty() || !P.jit[0].fn);
+  if (!scanned)  // every segment empty: nothing scanned, registers stay zero
+    for (int s = 0; s < n; ++s)
+      if (P.ksegs[size_t(s)].num_docs != 0) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL needs the query kernels");
+  alloc_outputs(ctx, P, B, nullptr, 0);
+  reset_outputs(P, B, st);
+  launch_scan(P, st);
+
+  // 2. the offers, on the same stream: one item per (HLL column, segment)
+  const uint64_t slots = ng > 0 ? P.dense_slots : 1;
+  DevBuf regs(ctx, nh * slots * kHllRegs * 4);
+  hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
+  std::vector<HllGroupItem> gitems;
+  std::vector<HllItem> items;
+  std::vector<int32_t> blob;
+  std::map<const std::vector<int32_t>*, size_t> roff;
+  for (int g = 0; g < ng; ++g)
+    if (!P.gdicts[size_t(g)].identity)
+      for (int s = 0; s < n; ++s) {
+        const std::vector<int32_t>* rm = P.gdicts[size_t(g)].remap[size_t(s)].get();
+        if (rm && !roff.count(rm)) {
+          roff[rm] = blob.size();
+          blob.insert(blob.end(), rm->begin(), rm->end());
+        }
+      }
+  DevBuf rdev(ctx, std::max<size_t>(1, blob.size()) * 4);
+  if (!blob.empty())
+    hip_check(hipMemcpyAsync(rdev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st), "remap H2D");
+  for (size_t k = 0; k < nh; ++k)
+    for (int s = 0; s < n; ++s) {
+      const StagedColumn& col = segs[s]->col(hcols[k]);
+      HllItem h{};
+      h.sel = P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)];
+      h.fwd = col.fwd;
+      h.codes = hll_code_table(ctx, col);
+      h.out = regs.as<uint32_t>() + k * slots * kHllRegs;
+      h.bits = col.bits;
+      h.num_docs = P.ksegs[size_t(s)].num_docs;
+      h.ncodes = col.card;
+      if (!h.fwd) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on a column without a forward index: " + col.name);
+      if (ng == 0) {
+        items.push_back(h);
+        continue;
+      }
+      HllGroupItem gi{};
+      gi.h = h;
+      for (int g = 0; g < ng; ++g) {
+        const StagedColumn& gc = segs[s]->col(q.group_cols[size_t(g)]);
+        if (!gc.fwd) fail(PGX_ERR_UNSUPPORTED, "GROUP BY a column without a forward index: " + gc.name);
+        gi.g[g].fwd = gc.fwd;
+        gi.g[g].bits = gc.bits;
+        const GlobalDict& gd = P.gdicts[size_t(g)];
+        if (!gd.identity && gd.remap[size_t(s)]) gi.g[g].remap = rdev.as<int32_t>() + roff[gd.remap[size_t(s)].get()];
+      }
+      gitems.push_back(gi);
+    }
+  const size_t nitems = ng == 0 ? items.size() : gitems.size();
+  const size_t isize = ng == 0 ? sizeof(HllItem) : sizeof(HllGroupItem);
+  const void* ihost = ng == 0 ? static_cast<const void*>(items.data()) : static_cast<const void*>(gitems.data());
+  DevBuf idev(ctx, std::max<size_t>(1, nitems) * isize);
+  if (nitems) hip_check(hipMemcpyAsync(idev.p, ihost, nitems * isize, hipMemcpyHostToDevice, st), "HLL items H2D");
+  const int G = hll_wgs(ctx, max_words, nitems);
+  if (scanned && nitems) {
+    if (ng == 0) {
+      PGX_LAUNCH(st, "pgx_hll_offer", pgx_launch_hll_offer(idev.as<HllItem>(), items.data(), int(nitems), G, st),
+                 "HLL offers");
+    } else {
+      PGX_LAUNCH(st, "pgx_hll_offer_group",
+                 pgx_launch_hll_offer_group(idev.as<HllGroupItem>(), gitems.data(), int(nitems), ng, K.gmul,
+                                            int64_t(slots), G, st),
+                 "HLL group offers");
+    }
+  }
+  pgx_result Rs;
+  finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
+
+  // 3. assemble in the request's order; numEntriesScannedPostFilter counts each HLL column among the projected ones
+  int extra = 0;
+  for (const auto& c : hcols)
+    if (std::find(qs.agg_col.begin(), qs.agg_col.end(), c) == qs.agg_col.end() &&
+        std::find(q.group_cols.begin(), q.group_cols.end(), c) == q.group_cols.end())
+      ++extra;
+  for (int i = 0; i < 4; ++i) R->stats[i] = Rs.stats[i];
+  R->stats[2] = Rs.stats[0] * (P.n_proj + extra);
+  R->num_aggs = na;
+  R->agg_fn = q.agg_fn;
+  R->top_n = q.top_n;
+  R->group_by = ng > 0;
+  R->mode = Rs.mode;
+  R->hll_pos = hll_pos;
+  const int64_t groups = ng > 0 ? Rs.num_groups : 1;
+  R->hll_groups = groups;
+  R->hll_regs.assign(nh * size_t(groups) * kHllRegs, 0);
+  if (ng == 0) {
+    std::vector<uint32_t> h32(nh * kHllRegs);
+    hip_check(hipMemcpy(h32.data(), regs.p, h32.size() * 4, hipMemcpyDeviceToHost), "HLL registers D2H");
+    for (size_t i = 0; i < h32.size(); ++i) R->hll_regs[i] = uint8_t(h32[i]);
+    R->agg_value.assign(size_t(na), 0.0);
+    R->agg_count.assign(size_t(na), 0);
+    for (int a = 0; a < na; ++a)
+      if (sv_pos[size_t(a)] >= 0) {
+        R->agg_value[size_t(a)] = Rs.agg_value[size_t(sv_pos[size_t(a)])];
+        R->agg_count[size_t(a)] = Rs.agg_count[size_t(sv_pos[size_t(a)])];
+      }
+    return;
+  }
+  R->num_groups = Rs.num_groups;
+  R->key_seg = std::move(Rs.key_seg);
+  R->key_id = std::move(Rs.key_id);
+  R->g_value.assign(size_t(na), std::vector<double>());
+  R->g_count.assign(size_t(na), std::vector<int64_t>());
+  for (int a = 0; a < na; ++a) {
+    if (sv_pos[size_t(a)] >= 0) {
+      R->g_value[size_t(a)] = std::move(Rs.g_value[size_t(sv_pos[size_t(a)])]);
+      R->g_count[size_t(a)] = std::move(Rs.g_count[size_t(sv_pos[size_t(a)])]);
+      // (two requests for the same standard function share nothing: each had its own slot in qs)
+    } else {
+      R->g_value[size_t(a)].assign(size_t(groups), 0.0);
+      R->g_count[size_t(a)].assign(size_t(groups), 0);
+    }
+  }
+  if (groups == 0) return;
+  // registers of the groups the result holds: their slots from the keys (global id x gmul), narrowed on the device
+  std::vector<int64_t> gslot(size_t(groups), 0);
+  for (int g = 0; g < ng; ++g) {
+    const GlobalDict& gd = P.gdicts[size_t(g)];
+    for (int64_t i = 0; i < groups; ++i) {
+      const int32_t s = R->key_seg[size_t(g)][size_t(i)], id = R->key_id[size_t(g)][size_t(i)];
+      if (s < 0 || s >= n) fail(PGX_ERR_INTERNAL, "group key without a segment");
+      const std::vector<int32_t>* rm = gd.identity ? nullptr : gd.remap[size_t(s)].get();
+      const int64_t gid = rm ? (*rm)[size_t(id)] : id;
+      gslot[size_t(i)] += gid * int64_t(K.gmul[g]);
+    }
+  }
+  for (int64_t i = 0; i < groups; ++i)
+    if (gslot[size_t(i)] < 0 || uint64_t(gslot[size_t(i)]) >= slots) fail(PGX_ERR_INTERNAL, "group slot out of range");
+  DevBuf sdev(ctx, size_t(groups) * 8), odev(ctx, size_t(groups) * kHllRegs);
+  hip_check(hipMemcpyAsync(sdev.p, gslot.data(), size_t(groups) * 8, hipMemcpyHostToDevice, st), "HLL slots H2D");
+  for (size_t k = 0; k < nh; ++k) {
+    PGX_LAUNCH(st, "pgx_hll_narrow",
+               pgx_launch_hll_narrow(regs.as<uint32_t>() + k * slots * kHllRegs, sdev.as<int64_t>(), groups,
+                                     int64_t(slots), odev.as<uint32_t>(), st),
+               "HLL narrow");
+    hip_check(hipMemcpyAsync(R->hll_regs.data() + k * size_t(groups) * kHllRegs, odev.p, size_t(groups) * kHllRegs,
+                             hipMemcpyDeviceToHost, st),
+              "HLL registers D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+  }
+}
+
+}  // namespace pgxh
+
+extern "C" {
+
+pgx_status pgx_hll_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
+                         uint16_t* codes) {
+  return guarded([&] {
+    if (n < 0 || (n > 0 && (!values || !codes))) fail(PGX_ERR_INVALID_ARG, "bad argument");
+    if (data_type < PGX_INT || data_type > PGX_STRING) fail(PGX_ERR_INVALID_ARG, "data type");
+    if (data_type == PGX_STRING && !string_offsets) fail(PGX_ERR_INVALID_ARG, "STRING values need offsets");
+    for (int64_t i = 0; i < n; ++i) {
+      int32_t h;
+      switch (data_type) {
+        case PGX_INT: h = static_cast<const int32_t*>(values)[i]; break;
+        case PGX_LONG: h = hash_long(static_cast<const int64_t*>(values)[i]); break;
+        case PGX_FLOAT: h = hash_float(static_cast<const float*>(values)[i]); break;
+        case PGX_DOUBLE: h = hash_double(static_cast<const double*>(values)[i]); break;
+        default: {
+          const int32_t a = string_offsets[i], b = string_offsets[i + 1];
+          if (a < 0 || b < a) fail(PGX_ERR_INVALID_ARG, "string offsets not ascending");
+          h = hash_utf8(static_cast<const uint8_t*>(values) + a, size_t(b - a));
+          break;
+        }
+      }
+      codes[i] = hll_code(h);
+    }
+  });
+}
+
+pgx_status pgx_result_hll(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
+                          uint8_t* registers) {
+  return guarded([&] {
+    if (r) r->ready();
+    if (!r) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
+    if (agg_index < 0 || agg_index >= r->num_aggs || size_t(agg_index) >= r->hll_pos.size() ||
+        r->hll_pos[size_t(agg_index)] < 0)
+      fail(PGX_ERR_INVALID_ARG, "not a DISTINCTCOUNTHLL function index");
+    if (first_group < 0 || num_groups < 0 || first_group > r->hll_groups || num_groups > r->hll_groups - first_group)
+      fail(PGX_ERR_INVALID_ARG, "group range outside the result");
+    if (num_groups == 0) return;
+    if (!registers) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    const size_t k = size_t(r->hll_pos[size_t(agg_index)]);
+    std::memcpy(registers, r->hll_regs.data() + (k * size_t(r->hll_groups) + size_t(first_group)) * kHllRegs,
+                size_t(num_groups) * kHllRegs);
+  });
+}
+
+}  // extern "C"

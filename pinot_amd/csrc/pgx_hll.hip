@@ -1,0 +1,326 @@
+// libpgx: DISTINCTCOUNTHLL registers -- DistinctCountHLLAggregationFunction (operator/aggregation/function/
+// DistinctCountHLLAggregationFunction.java:51-92: hll.offer((int) hashCode) per selected doc) over the selection bits
+// the query kernels wrote.  Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
+//
+// The hash depends on the dictionary value alone, so the host builds one u16 code per dictId (pgx_hll.cpp:
+// register << 8 | rank) and an offer is one gather and one register max.  Max is idempotent and order-free: the
+// registers are exact whatever the grid size or scheduling, and segments combine by maxing into the same registers.
+//
+//   pgx_hll_offer        grid (workgroups per item, items), one item per (segment, function).  A workgroup strides over
+//                        its item's 32-row mask words, one word per thread and step, skipping zero words.  Words with
+//                        many selected rows decode the column's 32 dictIds at once, sparse words read their rows one
+//                        by one.  Ranks are maxed into 256 u32 registers in LDS (read first, atomic only when greater:
+//                        after warm-up almost no offer changes a register); at the end thread t maxes a non-zero
+//                        register t into out[t].  A dense word goes in passes of independent accesses -- 32 code
+//                        gathers, 32 register reads, then the few atomics -- so that a wave has 32 loads in flight
+//                        instead of one chain of gather, read and compare per row.
+//   pgx_hll_offer_group  the same over (group slot, register) pairs: slot = sum of the group columns' global ids x
+//                        gmul (column 0 least significant), registers u32 in one table of slots x 256 in HBM, zeroed by
+//                        the caller.  u32 and not bytes: the hardware's 32-bit atomic max updates a register in one
+//                        instruction, where a byte register needs a compare-and-swap loop on its dword that retries
+//                        whenever any of the four neighbours changed; the price is 4 bytes per register to zero and a
+//                        narrowing pass (pgx_hll_narrow) over the groups the result holds.
+//   pgx_hll_narrow       one thread per (group, four registers): the listed slots' registers as bytes.
+// No workgroup waits on another; all stores are plain vector stores and vector atomics.
+#include <hip/hip_runtime.h>
+
+#include "pgx_internal.h"
+
+namespace pgx {
+
+__device__ __forceinline__ uint32_t hll_value(const uint32_t* __restrict__ fwd, int32_t row, int bits) {
+  const int64_t o = static_cast<int64_t>(row) * bits;
+  const uint32_t* w = fwd + (o >> 5);
+  const int s = static_cast<int>(o & 31);
+  const uint32_t mask = bits == 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+  const uint32_t hi = __builtin_bswap32(w[0]);
+  if (s + bits <= 32) return (hi >> (32 - s - bits)) & mask;  // (the next word may lie past the index: never read)
+  const uint64_t x = (static_cast<uint64_t>(hi) << 32) | __builtin_bswap32(w[1]);
+  return static_cast<uint32_t>(x >> (64 - s - bits)) & mask;
+}
+
+// The same without a branch: both dwords are always read.  For rows inside the padded index only (whole tiles plus 64
+// bytes: the second dword of the last row is still inside).
+__device__ __forceinline__ uint32_t hll_value2(const uint32_t* __restrict__ fwd, int32_t row, int bits) {
+  const int64_t o = static_cast<int64_t>(row) * bits;
+  const uint32_t* w = fwd + (o >> 5);
+  const int s = static_cast<int>(o & 31);
+  const uint64_t x = (static_cast<uint64_t>(__builtin_bswap32(w[0])) << 32) | __builtin_bswap32(w[1]);
+  return static_cast<uint32_t>((x << s) >> (64 - bits));
+}
+
+// The 32 dictIds of one mask word's rows of a B-bit forward index: B dwords, every one read once (streaming), then
+// constant-shift extraction (the layout of pgx_select.hip sel_decode32).
+template <int B>
+__device__ __forceinline__ void hll_decode32(const uint32_t* __restrict__ p, uint32_t (&v)[32]) {
+  uint32_t w[B + 1];
+#pragma unroll
+  for (int i = 0; i < B; ++i) w[i] = __builtin_bswap32(__builtin_nontemporal_load(p + i));
+  w[B] = 0;
+  constexpr uint32_t MASK = (B == 32) ? 0xFFFFFFFFu : ((1u << (B & 31)) - 1u);
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const int o = j * B, k = o >> 5, sh = o & 31;
+    if (sh + B <= 32) {
+      v[j] = (w[k] >> (32 - sh - B)) & MASK;
+    } else {
+      const uint64_t win = (static_cast<uint64_t>(w[k]) << 32) | w[k + 1];
+      v[j] = static_cast<uint32_t>(win >> (64 - sh - B)) & MASK;
+    }
+  }
+}
+
+#define PGX_HLL_CASES(X) \
+  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
+  X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+
+__device__ __forceinline__ void hll_decode_word(int bits, const uint32_t* __restrict__ fwd, int64_t word,
+                                                uint32_t (&v)[32]) {
+  const uint32_t* p = fwd + word * bits;
+  switch (bits) {
+#define PGX_HLL_CASE(b)    \
+  case b:                  \
+    hll_decode32<b>(p, v); \
+    break;
+    PGX_HLL_CASES(PGX_HLL_CASE)
+#undef PGX_HLL_CASE
+    default:
+#pragma unroll
+      for (int j = 0; j < 32; ++j) v[j] = 0;
+  }
+}
+
+constexpr int kHllDenseRows = 8;  // selected rows of a mask word from which the whole word's column is decoded
+
+// mask words of an item; an item with a count or width out of range, or an empty code table, has no rows
+__device__ __forceinline__ int hll_words(const HllItem& A) {
+  return A.num_docs > 0 && A.bits >= 1 && A.bits <= 32 && A.ncodes >= 1 ? (A.num_docs + 31) >> 5 : 0;
+}
+
+// mask word w of the item without the bits at and past num_docs (the spare word is never read: w < words)
+__device__ __forceinline__ uint32_t hll_mask_word(const HllItem& A, int64_t w) {
+  uint32_t sel = A.sel[w];
+  const int32_t left = A.num_docs - static_cast<int32_t>(w * 32);
+  if (left < 32) sel &= (1u << left) - 1u;
+  return sel;
+}
+
+// regs: 256 u32 registers (LDS or HBM)
+__device__ __forceinline__ void hll_offer(uint32_t* regs, const HllItem& A, uint32_t id) {
+  if (id >= static_cast<uint32_t>(A.ncodes)) return;
+  const uint32_t c = A.codes[id];
+  const uint32_t j = c >> 8, r = c & 0xFFu;
+  if (regs[j] < r) atomicMax(&regs[j], r);
+}
+
+// v[j]: the dictId of row j of a mask word -> its code, 0 for a row that is not selected or whose dictId lies at or
+// past the table (rank >= 1: a code is never 0).  ncodes >= 1 here: an empty table's item has no selected rows to offer.
+// The row's "on" state lives in its bit of sel and is applied as a mask on both sides of the load: a compare held
+// across the 32 loads in flight would take a pair of scalar registers per row.
+__device__ __forceinline__ void hll_gather_codes(const HllItem& A, uint32_t sel, uint32_t (&v)[32]) {
+#pragma unroll
+  for (int j = 0; j < 32; ++j) sel &= ~(static_cast<uint32_t>(v[j] >= static_cast<uint32_t>(A.ncodes)) << j);
+#pragma unroll
+  for (int j = 0; j < 32; ++j) {
+    const uint32_t on = 0u - ((sel >> j) & 1u);  // all ones or 0
+    v[j] = A.codes[v[j] & on] & on;
+  }
+}
+
+__global__ void __launch_bounds__(kHllBlock) pgx_hll_offer(const HllItem* __restrict__ items, int nitems) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  __shared__ uint32_t regs[kHllRegs];
+  const int tid = static_cast<int>(threadIdx.x);
+  regs[tid] = 0u;
+  __syncthreads();
+  const HllItem A = items[item];
+  const int words = hll_words(A);
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
+    const uint32_t sel = hll_mask_word(A, w);
+    if (sel == 0u) continue;
+    if (__builtin_popcount(sel) >= kHllDenseRows) {
+      // three passes over the word, each of 32 independent accesses the hardware keeps in flight together (a chain
+      // of gather, register read and compare per row leaves one access in flight per wave): the codes (entry 0 stands
+      // in for rows that offer nothing, so no load is conditional; a code is never 0), the registers, the few atomics
+      uint32_t v[32];
+      hll_decode_word(A.bits, A.fwd, w, v);
+      hll_gather_codes(A, sel, v);
+#pragma unroll
+      for (int j = 0; j < 32; ++j) v[j] = regs[v[j] >> 8] < (v[j] & 0xFFu) ? v[j] : 0u;
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        if (v[j] != 0u) atomicMax(&regs[v[j] >> 8], v[j] & 0xFFu);
+    } else {
+      const int32_t d0 = static_cast<int32_t>(w * 32);
+      for (uint32_t m = sel; m;) {
+        const int k = __builtin_ctz(m);
+        m &= m - 1u;
+        hll_offer(regs, A, hll_value(A.fwd, d0 + k, A.bits));
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t r = regs[tid];
+  if (r != 0u && A.out[tid] < r) atomicMax(&A.out[tid], r);
+}
+
+__device__ __forceinline__ void hll_offer_slot(const HllGroupItem& G, const HllGroupKey& K, int32_t row, uint32_t id) {
+  uint64_t slot = 0;
+  for (int g = 0; g < K.ngcols; ++g) {
+    int64_t gid = hll_value(G.g[g].fwd, row, G.g[g].bits);
+    if (G.g[g].remap) gid = G.g[g].remap[gid];
+    if (gid < 0) return;
+    slot += static_cast<uint64_t>(gid) * K.gmul[g];
+  }
+  if (slot >= K.slots) return;  // (a key outside the planned space: never written)
+  hll_offer(G.h.out + slot * kHllRegs, G.h, id);
+}
+
+// Rows J0 .. J0 + 15 of a mask word whose codes are gathered (v): slots, registers, atomics.  Half a word at a time:
+// 16 loads in flight per lane and pass, and half the addresses live at once.
+template <int J0>
+__device__ __forceinline__ void hll_group_rows(const HllGroupItem& G, const HllGroupKey& K, int32_t d0,
+                                               uint32_t (&v)[32]) {
+  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  for (int g = 0; g < K.ngcols; ++g) {
+    const uint32_t* __restrict__ gf = G.g[g].fwd;
+    const int32_t* __restrict__ rm = G.g[g].remap;
+    const int gb = G.g[g].bits;
+    const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+#pragma unroll
+    for (int j = J0; j < J0 + 16; ++j) {
+      // Masks, not compares: 32 compares hoisted above the loads would each hold a pair of scalar registers.
+      // on: the row still offers (its code field is not 0); a row that does not reads remap entry 0.
+      const uint32_t c16 = v[j] & 0xFFFFu;
+      const uint32_t on = static_cast<uint32_t>(static_cast<int32_t>(c16 | (0u - c16)) >> 31);
+      const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
+      const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
+      // 32-bit arithmetic throughout (a 64-bit multiply-add carries out into scalar registers too): an id of
+      // 65536 or more is outside every key space (bad); below that, slot so far + id * mul < 2^32, saturated to
+      // 2^17, and ok = it is below slots
+      const uint32_t hi = gid >> 16;
+      const uint32_t bad = static_cast<uint32_t>(static_cast<int32_t>(hi | (0u - hi)) >> 31);
+      const uint32_t s = __builtin_elementwise_min((v[j] >> 16) + (gid & 0xFFFFu) * mul, 0x20000u);
+      const uint32_t ok = ~static_cast<uint32_t>(static_cast<int32_t>(slots32 - 1u - s) >> 31) & ~bad;
+      v[j] = (c16 | (s << 16)) & ok & on;  // (a key outside the planned space: the row offers nothing)
+    }
+  }
+  uint32_t* const table = G.h.out;
+#pragma unroll
+  for (int j = J0; j < J0 + 16; ++j) {
+    const uint32_t cur = table[static_cast<size_t>(v[j] >> 16) * kHllRegs + ((v[j] >> 8) & 0xFFu)];
+    v[j] = cur < (v[j] & 0xFFu) ? v[j] : 0u;
+  }
+#pragma unroll
+  for (int j = J0; j < J0 + 16; ++j)
+    if (v[j] != 0u) atomicMax(&table[static_cast<size_t>(v[j] >> 16) * kHllRegs + ((v[j] >> 8) & 0xFFu)], v[j] & 0xFFu);
+}
+
+__global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupItem* __restrict__ items, int nitems,
+                                                                 const HllGroupKey K) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  const HllGroupItem& G = items[item];
+  const HllItem A = G.h;
+  const int tid = static_cast<int>(threadIdx.x);
+  int words = hll_words(A);
+  for (int g = 0; g < K.ngcols; ++g)
+    if (G.g[g].bits < 1 || G.g[g].bits > 32) words = 0;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
+    const uint32_t sel = hll_mask_word(A, w);
+    if (sel == 0u) continue;
+    const int32_t d0 = static_cast<int32_t>(w * 32);
+    if (__builtin_popcount(sel) >= kHllDenseRows) {
+      // passes of 32 independent accesses, as in pgx_hll_offer: the codes; per group column the rows' ids (the word's
+      // rows all lie inside the padded index, so the id loads are unconditional; a row that offers nothing takes
+      // remap entry 0) folded into the slot, which shares the word with the code (both fit 16 bits); the registers;
+      // the few atomics
+      uint32_t v[32];
+      hll_decode_word(A.bits, A.fwd, w, v);
+      hll_gather_codes(A, sel, v);
+      hll_group_rows<0>(G, K, d0, v);
+      hll_group_rows<16>(G, K, d0, v);
+    } else {
+      for (uint32_t m = sel; m;) {
+        const int k = __builtin_ctz(m);
+        m &= m - 1u;
+        hll_offer_slot(G, K, d0 + k, hll_value(A.fwd, d0 + k, A.bits));
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kHllBlock) pgx_hll_narrow(const uint32_t* __restrict__ table,
+                                                            const int64_t* __restrict__ slot, int64_t ngroups,
+                                                            uint64_t slots, uint32_t* __restrict__ out) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x;  // (group, register quad)
+  if (idx >= ngroups * (kHllRegs / 4)) return;
+  const int64_t g = idx / (kHllRegs / 4);
+  const int q = static_cast<int>(idx % (kHllRegs / 4));
+  const int64_t s = slot[g];
+  uint32_t packed = 0u;
+  if (s >= 0 && static_cast<uint64_t>(s) < slots) {
+    const uint32_t* r = table + s * kHllRegs + 4 * q;
+    packed = (r[0] & 0xFFu) | ((r[1] & 0xFFu) << 8) | ((r[2] & 0xFFu) << 16) | ((r[3] & 0xFFu) << 24);
+  }
+  out[idx] = packed;
+}
+
+}  // namespace pgx
+
+static bool hll_item_ok(const pgx::HllItem& h) {
+  return h.num_docs >= 0 && h.bits >= 1 && h.bits <= 32 && h.ncodes >= 0 && h.sel && h.fwd && h.codes && h.out;
+}
+
+// items: nitems descriptors in device memory; check: the caller's host copy of them, which is what gets validated.
+extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx::HllItem* check, int nitems,
+                                           int wgs_per_item, hipStream_t stream) {
+  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < nitems; ++i)
+    if (!hll_item_ok(check[i])) return hipErrorInvalidValue;
+  if (nitems == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_hll_offer, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
+                     dim3(pgx::kHllBlock), 0, stream, items, nitems);
+  return hipGetLastError();
+}
+
+// Every item's `h.out` is a table of slots x 256 u32 registers, zeroed by the caller.  gmul: ngcols host values.
+extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
+                                                 int nitems, int ngcols, const uint64_t* gmul, int64_t slots,
+                                                 int wgs_per_item, hipStream_t stream) {
+  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check || !gmul)
+    return hipErrorInvalidValue;
+  if (ngcols < 1 || ngcols > pgx::kMaxGroupCols || slots < 1 || slots > pgx::kHllMaxGroupSlots)
+    return hipErrorInvalidValue;
+  for (int g = 0; g < ngcols; ++g)
+    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return hipErrorInvalidValue;  // a mixed-radix layout
+  for (int i = 0; i < nitems; ++i) {
+    if (!hll_item_ok(check[i].h)) return hipErrorInvalidValue;
+    for (int g = 0; g < ngcols; ++g)
+      if (!check[i].g[g].fwd || check[i].g[g].bits < 1 || check[i].g[g].bits > 32) return hipErrorInvalidValue;
+  }
+  if (nitems == 0) return hipSuccess;
+  pgx::HllGroupKey K{};
+  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
+  K.slots = static_cast<uint64_t>(slots);
+  K.ngcols = ngcols;
+  hipLaunchKernelGGL(pgx::pgx_hll_offer_group, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
+                     dim3(pgx::kHllBlock), 0, stream, items, nitems, K);
+  return hipGetLastError();
+}
+
+// out: ngroups x 256 bytes (as ngroups x 64 dwords); group i's registers are those of table slot slot[i].
+extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t* slot, int64_t ngroups, int64_t slots,
+                                            uint32_t* out, hipStream_t stream) {
+  if (ngroups < 0 || slots < 1 || slots > pgx::kHllMaxGroupSlots || ngroups > slots || !table || !slot || !out)
+    return hipErrorInvalidValue;
+  if (ngroups == 0) return hipSuccess;
+  const int64_t blocks = (ngroups * (pgx::kHllRegs / 4) + pgx::kHllBlock - 1) / pgx::kHllBlock;
+  hipLaunchKernelGGL(pgx::pgx_hll_narrow, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kHllBlock), 0, stream, table,
+                     slot, ngroups, static_cast<uint64_t>(slots), out);
+  return hipGetLastError();
+}

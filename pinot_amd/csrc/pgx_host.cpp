@@ -1412,6 +1412,10 @@ void run_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n
     run_select(ctx, q, segs, n, bindings, opts, R, st);
     return;
   }
+  if (query_has_hll(q)) {  // DISTINCTCOUNTHLL: planned afresh every time as well
+    run_hll(ctx, q, segs, n, bindings, opts, R, st, dom);
+    return;
+  }
   // plan cache (single-device plans without a caller key domain; only plain plans are ever kept, so a hit is one)
   const bool cache = !dom && plan_cache_on() && n > 0;
   std::vector<uint64_t> uids;
@@ -1679,7 +1683,7 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* d, pgx_query** 
     auto q = std::make_unique<pgx_query>();
     for (int a = 0; a < d->num_aggs; ++a) {
       const int fn = d->aggs[a].fn;
-      if (fn < PGX_COUNT || fn > PGX_AVGMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
+      if (fn < PGX_COUNT || fn > PGX_DISTINCTCOUNTHLL) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
       q->agg_fn.push_back(fn);
       const char* c = d->aggs[a].column;
       std::string col = (c && std::strcmp(c, "*") != 0) ? c : "";
@@ -1704,6 +1708,7 @@ pgx_status pgx_query_set_key_domain(pgx_query* q, int32_t group_col, int32_t typ
   return guarded([&] {
     if (!q) fail(PGX_ERR_INVALID_ARG, "NULL query");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "key domains on a selection query");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "key domains with DISTINCTCOUNTHLL");
     if (group_col < 0 || group_col >= int(q->group_cols.size())) fail(PGX_ERR_INVALID_ARG, "group column index");
     plan_cache_purge(q, nullptr);  // plans decode keys against the domain
     if (num_values < 0 || num_values > INT32_MAX) fail(PGX_ERR_INVALID_ARG, "key domain size");
@@ -1846,6 +1851,7 @@ pgx_status pgx_execute_multi(pgx_ctx* const* ctxs, int32_t nctx, const pgx_query
     if (opts && (opts->stream || opts->dense_out || (opts->flags & PGX_X_KEEP_DENSE_ON_DEVICE)))
       fail(PGX_ERR_INVALID_ARG, "pgx_execute_multi takes flags only (each context runs on its own stream)");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_multi on a selection query");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_multi with DISTINCTCOUNTHLL");
     auto R = std::make_unique<pgx_result>();
     run_multi(ctxs, nctx, *q, segs, n, bindings, opts ? opts->flags : 0, R.get());
     *out = R.release();
@@ -1912,6 +1918,7 @@ pgx_status pgx_result_agg(const pgx_result* r, int32_t fn, double* value, int64_
     if (r->group_by) fail(PGX_ERR_INVALID_ARG, "group-by result");
     if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
     if (fn < 0 || fn >= r->num_aggs) fail(PGX_ERR_INVALID_ARG, "function index");
+    if (r->is_hll(fn)) fail(PGX_ERR_INVALID_ARG, "DISTINCTCOUNTHLL function: read its registers with pgx_result_hll");
     if (value) *value = r->agg_value[fn];
     if (count) *count = r->agg_count[fn];
   });
@@ -1942,6 +1949,7 @@ pgx_status pgx_result_group_values(const pgx_result* r, int32_t fn, double* valu
     if (r) r->ready();
     if (!r || !r->group_by) fail(PGX_ERR_INVALID_ARG, "not a group-by result");
     if (fn < 0 || fn >= r->num_aggs) fail(PGX_ERR_INVALID_ARG, "function index");
+    if (r->is_hll(fn)) fail(PGX_ERR_INVALID_ARG, "DISTINCTCOUNTHLL function: read its registers with pgx_result_hll");
     const_cast<pgx_result*>(r)->materialize();
     if (value) std::memcpy(value, r->g_value[fn].data(), r->num_groups * 8);
     if (count) std::memcpy(count, r->g_count[fn].data(), r->num_groups * 8);
@@ -1962,6 +1970,7 @@ pgx_status pgx_result_trim(const pgx_result* r, int32_t fn, int64_t* idx, int64_
     if (r) r->ready();
     if (!r || !r->group_by || !n) fail(PGX_ERR_INVALID_ARG, "not a group-by result");
     if (fn < 0 || fn >= r->num_aggs) fail(PGX_ERR_INVALID_ARG, "function index");
+    if (r->is_hll(fn)) fail(PGX_ERR_INVALID_ARG, "DISTINCTCOUNTHLL function: its intermediates have no order to trim by");
     const int64_t min_trim = std::max<int64_t>(r->top_n, 1000);
     const int64_t threshold = min_trim * 20, size = min_trim * 5;
     std::vector<int64_t> order;
@@ -2035,6 +2044,7 @@ pgx_status pgx_query_dense_slots(const pgx_query* q, pgx_segment* const* segs, i
   return guarded([&] {
     if (!q || !segs || !slots) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL queries have no dense table");
     if (!q->group_cols.empty() && query_is_mv(*q, segs, n)) {  // multi-value group-by: merged by key, never densely
       *slots = -1;
       return;
@@ -2050,6 +2060,7 @@ pgx_status pgx_query_dense_plane_op(const pgx_query* q, pgx_segment* const* segs
   return guarded([&] {
     if (!q || !segs || !op) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL queries have no dense table");
     if (plane == 0) { *op = P_ADD_I64; return; }
     if (plane < 1 || plane > int(q->agg_fn.size())) fail(PGX_ERR_INVALID_ARG, "plane");
     const int fn = q->agg_fn[plane - 1];
@@ -2065,6 +2076,7 @@ pgx_status pgx_result_from_dense(pgx_ctx* ctx, const pgx_query* q, pgx_segment* 
   return guarded([&] {
     if (!ctx || !q || !segs || !dense_device || !out) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "selection queries have no dense table");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL queries have no dense table");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ExecPlan P;
     std::vector<pgx_leaf_binding> none(size_t(n) * q->leaf_col.size(), pgx_leaf_binding{0, -1, nullptr});
@@ -2241,6 +2253,7 @@ pgx_status pgx_execute_timed(pgx_ctx* ctx, const pgx_query* q, pgx_segment* cons
   return guarded([&] {
     if (!ctx || !q || !segs || iters < 1) fail(PGX_ERR_INVALID_ARG, "bad argument");
     if (q->select) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_timed on a selection query");
+    if (query_has_hll(*q)) fail(PGX_ERR_UNSUPPORTED, "pgx_execute_timed with DISTINCTCOUNTHLL");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = ctx->stream;
     ExecPlan P;

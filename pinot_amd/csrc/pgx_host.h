@@ -123,6 +123,13 @@ extern "C" hipError_t pgx_launch_select_merge(int nitems, int K, int wgs_per_ite
 extern "C" hipError_t pgx_launch_select_gather(const pgx::SelGatherCol* cols, int nitems, int ncols, int K,
                                                const int32_t* out_doc, const int32_t* out_cnt, int32_t* out_ids,
                                                hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx::HllItem* check, int nitems,
+                                           int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
+                                                 int nitems, int ngcols, const uint64_t* gmul, int64_t slots,
+                                                 int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t* slot, int64_t ngroups, int64_t slots,
+                                            uint32_t* out, hipStream_t stream);
 struct pgx_ctx;
 extern "C" void ctx_unref(pgx_ctx* ctx);
 
@@ -506,6 +513,7 @@ struct SharedDict {
   // -1 does not fit (guarded by the context's dict_mu)
   DevBuf pk_img;
   int pk_state = 0, pk_sh = 0, pk_words = 0;
+  DevBuf hll_codes;  // DISTINCTCOUNTHLL: u16 register << 8 | rank per dictId, built on first use (pgx_hll.cpp; dict_mu)
 };
 constexpr int kNarrowImg4Words = (160 * 1024 - 16 * 192 * 20 - 1024) / 4;  // pgx_narrow.hip kNAImg4Words
 
@@ -547,6 +555,7 @@ struct StagedColumn {
   int64_t total_entries = 0;
   DevBuf mv_start;
   int max_mv = 0;
+  mutable DevBuf hll_codes;  // STRING columns: the DISTINCTCOUNTHLL code table (numeric: shared->hll_codes)
 };
 
 inline std::atomic<uint64_t> g_segment_uid{1};
@@ -739,6 +748,12 @@ struct pgx_result {
   std::vector<std::string> sel_schema;
   std::vector<int32_t> sel_counts, sel_seg, sel_doc;
   std::vector<int32_t> sel_ids;  // [schema column][row]
+  // DISTINCTCOUNTHLL (run_hll): per function its register block (-1: a standard function), the number of groups
+  // (1 for an aggregation-only result) and the registers, [block][group][256]
+  std::vector<int> hll_pos;
+  int64_t hll_groups = 0;
+  std::vector<uint8_t> hll_regs;
+  bool is_hll(int fn) const { return size_t(fn) < hll_pos.size() && hll_pos[size_t(fn)] >= 0; }
   std::unique_ptr<AsyncState> async;  // declared last: destroyed (joined) before the fields its thread writes
   void ready() const;                 // waits for an async execution; throws its error
   void materialize();
@@ -1104,6 +1119,12 @@ void run_mv_group(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, in
 
 void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
                 const pgx_exec_opts* opts, pgx_result* R, hipStream_t st);  // pgx_select.cpp
+
+void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
+             const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom);  // pgx_hll.cpp
+inline bool query_has_hll(const pgx_query& q) {
+  return std::find(q.agg_fn.begin(), q.agg_fn.end(), int(PGX_DISTINCTCOUNTHLL)) != q.agg_fn.end();
+}
 
 void parse_star_tree(pgx_segment& seg);
 void stage_column(pgx_ctx* ctx, pgx_segment* seg, const pgx_column_desc& d, bool device_mem, StagedColumn& c);

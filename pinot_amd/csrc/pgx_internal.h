@@ -139,6 +139,40 @@ struct SelGatherCol {          // one schema column of one item (pgx_select_gath
   int32_t pad;
 };
 
+// DISTINCTCOUNTHLL (pgx_hll.hip; DistinctCountHLLAggregationFunction over stream-lib's HyperLogLog(log2m = 8)): one
+// item per (segment, function).  codes[dictId] = register << 8 | rank of offer((int) hashCode(value)); the registers
+// are u32 and only ever maxed into, so items that share `out` combine.
+constexpr int kHllRegs = 256;
+constexpr int kHllBlock = 256;
+constexpr int kHllMaxGroupSlots = 65536;  // pgx.h PGX_HLL_MAX_GROUP_SLOTS
+struct HllItem {
+  const uint32_t* sel;         // selected docs: bit (d & 31) of word d >> 5 (written by the query kernel)
+  const uint32_t* fwd;         // packed big-endian fixed-bit forward index, padded to whole tiles
+  const uint16_t* codes;       // ncodes entries
+  uint32_t* out;               // 256 registers; the group kernel: slots x 256
+  int32_t bits;
+  int32_t num_docs;
+  int32_t ncodes;              // dictIds at or past it are never looked up
+  int32_t pad;
+};
+struct HllGCol {               // one group column of one segment
+  const uint32_t* fwd;
+  const int32_t* remap;        // segment dictId -> global id (null: identity)
+  int32_t bits;
+  int32_t pad;
+};
+struct HllGroupItem {
+  HllItem h;
+  HllGCol g[kMaxGroupCols];
+};
+static_assert(sizeof(HllItem) == 48 && sizeof(HllGroupItem) == 48 + kMaxGroupCols * 24, "tests/hll_ref.py mirrors these");
+struct HllGroupKey {           // passed by value: slot = sum over the group columns of global id x gmul
+  uint64_t gmul[kMaxGroupCols];
+  uint64_t slots;
+  int32_t ngcols;
+  int32_t pad;
+};
+
 // Statistics automaton over one segment's leaf masks (pgx_kernels.hip pgx_fsm_chunks / pgx_fsm_compose).
 struct FsmSeg {
   const uint32_t* lmask;       // leaf l, row r: bit (r & 31) of word [l * words + (r >> 5)]

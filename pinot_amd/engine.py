@@ -28,7 +28,8 @@ from .segment import Column, SegmentData
 
 _DT = {"INT": N.PGX_INT, "LONG": N.PGX_LONG, "FLOAT": N.PGX_FLOAT, "DOUBLE": N.PGX_DOUBLE, "STRING": N.PGX_STRING}
 _FN = {"count": N.PGX_COUNT, "sum": N.PGX_SUM, "min": N.PGX_MIN, "max": N.PGX_MAX, "avg": N.PGX_AVG,
-       "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV}
+       "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV,
+       "distinctcounthll": N.PGX_DISTINCTCOUNTHLL}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -729,6 +730,14 @@ def render_key(q: _Query, segments: Sequence[IndexSegment], g: int, seg_index: i
     return segments[seg_index].column(q.group_cols[g]).string_of(int(dict_id))
 
 
+def result_hll(r, fn_index: int, first_group: int = 0, num_groups: int = 1) -> np.ndarray:
+    """pgx_result_hll: the HyperLogLog registers of a DISTINCTCOUNTHLL function, uint8 [num_groups, 256] (one "group"
+    for an aggregation-only result)."""
+    regs = np.zeros((max(num_groups, 1), 256), dtype=np.uint8)
+    N.check(N.lib().pgx_result_hll(r, fn_index, first_group, num_groups, regs.ctypes.data))
+    return regs[:num_groups]
+
+
 def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = False) -> IntermediateResultsBlock:
     L = N.lib()
     st = (C.c_int64 * 4)()
@@ -737,6 +746,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if not q.group_cols:
         out = []
         for i, fn in enumerate(q.fns):
+            if fn == "distinctcounthll":  # the intermediate is the register set (hll.py)
+                out.append(result_hll(r, i)[0])
+                continue
             v, c = C.c_double(), C.c_int64()
             N.check(L.pgx_result_agg(r, i, C.byref(v), C.byref(c)))
             if fn in ("count", "countmv"):
@@ -763,6 +775,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     keys = ["\t".join(p[i] for p in key_parts) for i in range(n)]
     vals = []
     for i, fn in enumerate(q.fns):
+        if fn == "distinctcounthll":
+            vals.append(list(result_hll(r, i, 0, n)))
+            continue
         v = np.zeros(max(n, 1), dtype=np.float64)
         c = np.zeros(max(n, 1), dtype=np.int64)
         N.check(L.pgx_result_group_values(r, i, v.ctypes.data, c.ctypes.data))
@@ -778,6 +793,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if trim:
         trimmed = []
         for i in range(len(q.fns)):
+            if q.fns[i] == "distinctcounthll":  # no order to trim by: every group (pgx_result_trim refuses the index)
+                trimmed.append({keys[j]: per_group[j][i] for j in range(n)})
+                continue
             cap = C.c_int64(n)
             idx = np.zeros(max(n, 1), dtype=np.int64)
             N.check(L.pgx_result_trim(r, i, idx.ctypes.data, C.byref(cap)))

@@ -10,9 +10,10 @@ decomposed on the host into GPU sub-queries the fused scan kernels already run:
   DistinctCountAggregationFunction.java aggregate), so STRING columns are supported and FLOAT 0.25 / 0.75 stay distinct;
 * PERCENTILEnn(c) -> the same ``GROUP BY c`` histogram; intermediate the (value, count) pairs in value order, i.e. the
   reference's DoubleArrayList of every selected value (PercentileAggregationFunction.java aggregate) held as a multiset;
-* DISTINCTCOUNTHLL(c) -> the same histogram; intermediate the HyperLogLog registers of the distinct hash codes
-  (operator/aggregation/function/DistinctCountHLLAggregationFunction.java aggregate: hll.offer((int) hash)), which
-  depend only on that set (hll.py).
+* DISTINCTCOUNTHLL(c) -> a function of the base query itself (PGX_DISTINCTCOUNTHLL: the registers are built on the
+  device and read with pgx_result_hll; ``native_hll``).  Where the library refuses the shape, or with PGX_HLL_NATIVE=0,
+  the same histogram; intermediate the HyperLogLog registers of the distinct hash codes (operator/aggregation/function/
+  DistinctCountHLLAggregationFunction.java aggregate: hll.offer((int) hash)), which depend only on that set (hll.py).
 
 One histogram sub-query serves every DISTINCTCOUNT / PERCENTILE over the same column.  Statistics are the base query's,
 with numEntriesScannedPostFilter counted over the ORIGINAL projection columns (AggregationOperator.java:93-98).
@@ -23,6 +24,7 @@ hands those functions String[] values and their aggregate() requires double[]).
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, List, Sequence
 
 import numpy as np
@@ -130,14 +132,31 @@ def _projection_count(request: dict) -> int:
     return len(cols)
 
 
-def _base_request(request: dict):
-    """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE) and, per original
-    function, its base slot: an index, a (min, max) index pair, or None (histogram functions)."""
+def native_hll(request: dict, segments) -> bool:
+    """Whether the request's single-value DISTINCTCOUNTHLL functions run inside the base query (PGX_DISTINCTCOUNTHLL:
+    registers computed on the device, pgx_hll.hip) instead of through the ``GROUP BY c`` histogram.  PGX_HLL_NATIVE=0
+    forces the histogram (A/B, tests).  The native query never uses a star tree (every raw row is offered), so a request
+    whose base query a star tree could answer keeps the decomposition, and with it its statistics."""
+    if os.environ.get("PGX_HLL_NATIVE", "1") == "0":
+        return False
+    if not any(a["fn"] == "distinctcounthll" for a in request["aggregations"]):
+        return False
+    use_st = str((request.get("debug_options") or {}).get("useStarTree", "true")).lower() != "false"
+    return not (use_st and any(getattr(s.data, "star_tree", None) is not None for s in segments))
+
+
+def _base_request(request: dict, native: bool = False):
+    """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE; with `native` the
+    DISTINCTCOUNTHLL functions as well) and, per original function, its base slot: an index, a (min, max) index pair,
+    or None (histogram functions)."""
     base = [{"fn": "count", "column": "*"}]
     slot = []
     for a in request["aggregations"]:
         fn = a["fn"]
-        if fn == "minmaxrange":
+        if native and fn == "distinctcounthll":
+            base.append(dict(a))
+            slot.append(len(base) - 1)
+        elif fn == "minmaxrange":
             base += [{"fn": "min", "column": a["column"]}, {"fn": "max", "column": a["column"]}]
             slot.append((len(base) - 2, len(base) - 1))
         elif fn in _HIST_FNS or fn.startswith("percentile") or fn in EXT_MV_FUNCTIONS:
@@ -152,11 +171,13 @@ def _dtype(segments, col: str) -> str:
     return segments[0].column(col).meta.data_type if segments else "INT"
 
 
-def _hist_columns(request: dict, segments) -> List[str]:
+def _hist_columns(request: dict, segments, native: bool = False) -> List[str]:
     cols = []
     for a in request["aggregations"]:
         mv = a["fn"] in EXT_MV_FUNCTIONS
         fn = base_fn(a["fn"])
+        if native and a["fn"] == "distinctcounthll":  # in the base query: no histogram on its account
+            continue
         if fn not in _HIST_FNS and fn != "minmaxrange" and not fn.startswith("percentile"):
             continue
         if segments and bool(segments[0].column(a["column"]).meta.is_mv) != mv:
@@ -192,13 +213,13 @@ def _numeric(hist) -> List:
     return [(float(v), c) for v, c in hist]
 
 
-def _run_group_by(ctx, request, segments, combine) -> E.IntermediateResultsBlock:
+def _run_group_by(ctx, request, segments, combine, native: bool = False) -> E.IntermediateResultsBlock:
     """Group-by: the base request keeps the GROUP BY columns; each histogram column c runs ``GROUP BY <columns>, c``
     with COUNT(*), and its groups are folded back per leading key (the group string minus its last field).  The
     combine trim keeps the base request's trimmed maps for the standard functions; functions whose intermediates the
     reference cannot order keep every group (AggregationGroupByOperatorService.java:336-349)."""
     gb = request["group_by"]
-    base, slot = _base_request(request)
+    base, slot = _base_request(request, native)
     bq = E._Query(ctx, {"aggregations": base, "group_by": dict(gb), "filter": request.get("filter")})
     r = bq.execute(segments)
     try:
@@ -209,7 +230,7 @@ def _run_group_by(ctx, request, segments, combine) -> E.IntermediateResultsBlock
     bmap = bblk.get_aggregation_group_by_result().as_map()
     ng = len(gb["columns"])
     hists: Dict[str, Dict[str, List]] = {}
-    for c in _hist_columns(request, segments):
+    for c in _hist_columns(request, segments, native):
         hq = E._Query(ctx, {"aggregations": [{"fn": "count", "column": "*"}],
                             "group_by": {"columns": list(gb["columns"]) + [c], "top_n": gb.get("top_n", 10)},
                             "filter": request.get("filter")})
@@ -239,7 +260,7 @@ def _run_group_by(ctx, request, segments, combine) -> E.IntermediateResultsBlock
             return (float(bvals[s[0]]), float(bvals[s[1]]))
         if fn == "distinctcount":
             return _hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, []))
-        if fn == "distinctcounthll":
+        if fn == "distinctcounthll" and s is None:
             return HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, [])))
         if fn == "fasthll":
             return _fast_hll(hists[a["column"]].get(key, []))
@@ -270,10 +291,20 @@ def _run_group_by(ctx, request, segments, combine) -> E.IntermediateResultsBlock
 
 def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
         combine: bool = True) -> E.IntermediateResultsBlock:
+    if native_hll(request, segments):
+        try:
+            return _run(ctx, request, segments, combine, True)
+        except N.PgxError as e:  # a shape the native path refuses runs as the decomposition
+            if e.status != N.PGX_ERR_UNSUPPORTED:
+                raise
+    return _run(ctx, request, segments, combine, False)
+
+
+def _run(ctx, request, segments, combine, native) -> E.IntermediateResultsBlock:
     if request.get("group_by"):
-        return _run_group_by(ctx, request, segments, combine)
+        return _run_group_by(ctx, request, segments, combine, native)
     aggs = request["aggregations"]
-    base, slot = _base_request(request)
+    base, slot = _base_request(request, native)
     bq = E._Query(ctx, {"aggregations": base, "group_by": None, "filter": request.get("filter")})
     r = bq.execute(segments)
     try:
@@ -282,7 +313,7 @@ def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
         N.lib().pgx_result_release(r)
         bq.close()
     hists = {}
-    for c in _hist_columns(request, segments):
+    for c in _hist_columns(request, segments, native):
         hq = E._Query(ctx, {"aggregations": [{"fn": "count", "column": "*"}],
                             "group_by": {"columns": [c], "top_n": 10}, "filter": request.get("filter")})
         r = hq.execute(segments)
@@ -304,7 +335,7 @@ def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
             out.append((float(base_res[s[0]]), float(base_res[s[1]])))
         elif fn == "distinctcount":
             out.append(_hash_set(_dtype(segments, a["column"]), hists[a["column"]]))
-        elif fn == "distinctcounthll":
+        elif fn == "distinctcounthll" and s is None:
             out.append(HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]])))
         elif fn == "fasthll":
             out.append(_fast_hll(hists[a["column"]]))

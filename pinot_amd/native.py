@@ -19,6 +19,8 @@ class PgxError(RuntimeError):
 
 PGX_INT, PGX_LONG, PGX_FLOAT, PGX_DOUBLE, PGX_STRING = range(5)
 PGX_COUNT, PGX_SUM, PGX_MIN, PGX_MAX, PGX_AVG, PGX_COUNTMV, PGX_SUMMV, PGX_MINMV, PGX_MAXMV, PGX_AVGMV = range(10)
+PGX_DISTINCTCOUNTHLL = 10
+PGX_HLL_MAX_GROUP_SLOTS = 65536
 PGX_PRED = {"EQ": 0, "NEQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 PGX_F_LEAF, PGX_F_AND, PGX_F_OR = 0, 1, 2
 PGX_MEM_HOST, PGX_MEM_DEVICE = 0, 1
@@ -175,6 +177,8 @@ EXPORTS = {
     "pgx_mutable_snapshot": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "pgx_mutable_num_docs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pgx_mutable_release": (C.c_int, [C.c_void_p]),
+    "pgx_result_hll": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "pgx_hll_codes": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "pgx_timing_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]),
 }
 
