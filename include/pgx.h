@@ -40,7 +40,7 @@ extern "C" {
 #define PGX_ABI_VERSION 8  /* 7: pgx_mutable_* (realtime segments in place); 8: pgx_result_record_words, records of
                               * every device-resident layout (several value columns, f64 sums); pgx_select_compile and
                               * pgx_result_select_* were added under 8: new entry points only, no existing struct or
-                              * call changed; likewise PGX_DISTINCTCOUNTHLL, pgx_result_hll and pgx_hll_codes */
+                              * call changed; likewise PGX_DISTINCTCOUNTHLL[MV], pgx_result_hll and pgx_hll_codes */
 
 typedef enum {
   PGX_OK = 0,
@@ -58,10 +58,11 @@ typedef enum { PGX_INT = 0, PGX_LONG = 1, PGX_FLOAT = 2, PGX_DOUBLE = 3, PGX_STR
  * (operator/aggregation/function/{Count,Sum,Min,Max,Avg}MVAggregationFunction.java); aggregation-only queries. */
 /* PGX_DISTINCTCOUNTHLL (operator/aggregation/function/DistinctCountHLLAggregationFunction.java): a single-value
  * column of any of the five data types; its intermediate is 256 HyperLogLog registers per result (per group), read
- * with pgx_result_hll (below, "DISTINCTCOUNTHLL"). */
+ * with pgx_result_hll (below, "DISTINCTCOUNTHLL").  PGX_DISTINCTCOUNTHLLMV (DistinctCountHLLMVAggregationFunction.java)
+ * is the same over every value of a multi-value column in the selected docs. */
 typedef enum { PGX_COUNT = 0, PGX_SUM = 1, PGX_MIN = 2, PGX_MAX = 3, PGX_AVG = 4,
                PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9,
-               PGX_DISTINCTCOUNTHLL = 10 } pgx_agg_fn;
+               PGX_DISTINCTCOUNTHLL = 10, PGX_DISTINCTCOUNTHLLMV = 11 } pgx_agg_fn;
 
 /* Predicate kinds (common/Predicate.java Type); they select the physical filter operator exactly as
  * plan/FilterPlanNode.java:118-132 does and drive the numEntriesScannedInFilter statistic. */
@@ -374,13 +375,23 @@ pgx_status pgx_result_gather(const pgx_result* r, const int64_t* group_index, in
  * groups in the order of pgx_result_group_keys / _values; an aggregation-only result has exactly one group
  * (first_group 0, num_groups 1).  The registers are those of stream-lib's HyperLogLog(log2m = 8) after
  * offer((int) hashCode(value)) of every selected doc's value: exact, whatever the order.  PGX_ERR_INVALID_ARG: agg_index
- * is not a PGX_DISTINCTCOUNTHLL function, or the range lies outside the result.
+ * is not a PGX_DISTINCTCOUNTHLL[MV] function, or the range lies outside the result.
+ * PGX_DISTINCTCOUNTHLLMV offers every value of every selected doc of a multi-value column (one slot per doc under
+ * GROUP BY: the doc's single-value group columns).  Same registers, same accessor, same statistics: its column counts
+ * once among the projected ones (docs x columns, not docs x values).  It mixes with PGX_DISTINCTCOUNTHLL and the
+ * standard single-value functions in any order; two functions over one column share their registers.  The function's
+ * column must be multi-value in every executed segment ("multi-value function on single-value column" otherwise), as
+ * PGX_DISTINCTCOUNTHLL's must be single-value.  pgx_query_compile already returns that PGX_ERR_UNSUPPORTED when the
+ * context holds staged segments with a column of that name and every one of them holds it single-value; a column no
+ * staged segment has, or one that is multi-value somewhere, compiles, and the execution checks its own segments.  The filter may hold leaves on multi-value columns.
  * Numeric accessors on an HLL function index: those that address ONE function -- pgx_result_agg,
  * pgx_result_group_values, pgx_result_trim -- return PGX_ERR_INVALID_ARG; pgx_result_gather, which returns every
  * function at once, puts value 0 and count 0 there.
  * PGX_ERR_UNSUPPORTED (the caller falls back): under GROUP BY a key space that is not dense (hash or partitioned keys,
  * PGX_X_FORCE_HASH) or has more than PGX_HLL_MAX_GROUP_SLOTS slots (the product of the group columns' cardinalities
- * over the executed segments); a multi-value column, group column or function in the same query; pgx_execute_multi;
+ * over the executed segments); PGX_DISTINCTCOUNTHLL on a multi-value column or PGX_DISTINCTCOUNTHLLMV on a
+ * single-value one; a multi-value group column or a standard multi-value function (PGX_COUNTMV .. PGX_AVGMV) in the
+ * same query; pgx_execute_multi;
  * key domains; a caller's dense table (dense_out, PGX_X_KEEP_DENSE_ON_DEVICE, pgx_query_dense_slots and the other
  * dense-table calls); pgx_execute_timed; PGX_JIT=0. */
 #define PGX_HLL_MAX_GROUP_SLOTS 65536

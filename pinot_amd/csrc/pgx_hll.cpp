@@ -107,9 +107,11 @@ static int hll_wgs(const pgx_ctx* ctx, int max_words, size_t nitems) {
   return std::min(G, 64);
 }
 
-// A query with DISTINCTCOUNTHLL functions: the rest of it (its filter, its standard functions or COUNT(*) alone, its
-// GROUP BY) runs through the query kernels, which also write every scanned row's selection bit; pgx_hll_offer
-// [_group] then offers every selected row's code.  Planned afresh every time (no plan cache).
+// A query with DISTINCTCOUNTHLL / DISTINCTCOUNTHLLMV functions: the rest of it (its filter, its standard functions or
+// COUNT(*) alone, its GROUP BY) runs through the query kernels, which also write every scanned row's selection bit;
+// pgx_hll_offer[_group] then offers every selected row's code, pgx_hll_offer_mv[_group] the code of every value of
+// every selected doc of a multi-value column (DistinctCountHLLMVAggregationFunction.java).  Planned afresh every time
+// (no plan cache).
 void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
              const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom) {
   const uint32_t xflags = opts ? opts->flags : 0;
@@ -126,18 +128,28 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   qs.agg_fn.clear();
   qs.agg_col.clear();
   std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1);
-  std::vector<std::string> hcols;
+  std::vector<std::string> hcols;  // a column is single-value or multi-value, so the name identifies the block
+  std::vector<char> hmv;           // per HLL column: multi-value (DISTINCTCOUNTHLLMV)
   for (int a = 0; a < na; ++a) {
     const int f = q.agg_fn[size_t(a)];
-    if (f == PGX_DISTINCTCOUNTHLL) {
+    if (f == PGX_DISTINCTCOUNTHLL || f == PGX_DISTINCTCOUNTHLLMV) {
       const std::string& c = q.agg_col[size_t(a)];
-      for (int s = 0; s < n; ++s)
-        if (segs[s]->col(c).is_mv) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on multi-value column " + c);
+      const bool mv = f == PGX_DISTINCTCOUNTHLLMV;
+      for (int s = 0; s < n; ++s) {
+        const bool is_mv = segs[s]->col(c).is_mv;
+        if (!mv && is_mv) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on multi-value column " + c);
+        if (mv && !is_mv) fail(PGX_ERR_UNSUPPORTED, "multi-value function on single-value column " + c);
+      }
       auto it = std::find(hcols.begin(), hcols.end(), c);
       hll_pos[size_t(a)] = int(it - hcols.begin());
-      if (it == hcols.end()) hcols.push_back(c);
+      if (it == hcols.end()) {
+        hcols.push_back(c);
+        hmv.push_back(mv);
+      }
     } else {
-      if (f >= PGX_COUNTMV) fail(PGX_ERR_UNSUPPORTED, "multi-value functions together with DISTINCTCOUNTHLL");
+      if (f < PGX_COUNT || f > PGX_AVGMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
+      if (is_standard_mv_fn(f))
+        fail(PGX_ERR_UNSUPPORTED, "standard multi-value functions together with DISTINCTCOUNTHLL");
       sv_pos[size_t(a)] = int(qs.agg_fn.size());
       qs.agg_fn.push_back(f);
       qs.agg_col.push_back(q.agg_col[size_t(a)]);
@@ -188,6 +200,8 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
   std::vector<HllGroupItem> gitems;
   std::vector<HllItem> items;
+  std::vector<HllMvGroupItem> mgitems;  // DISTINCTCOUNTHLLMV: the same with the docs' value ranges
+  std::vector<HllMvItem> mitems;
   std::vector<int32_t> blob;
   std::map<const std::vector<int32_t>*, size_t> roff;
   for (int g = 0; g < ng; ++g)
@@ -214,8 +228,12 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
       h.num_docs = P.ksegs[size_t(s)].num_docs;
       h.ncodes = col.card;
       if (!h.fwd) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on a column without a forward index: " + col.name);
+      const int32_t* start = hmv[k] ? col.mv_start.as<const int32_t>() : nullptr;
+      if (hmv[k] && (!start || col.total_entries < 0 || col.total_entries > INT32_MAX))
+        fail(PGX_ERR_INTERNAL, "multi-value column without value ranges: " + col.name);
       if (ng == 0) {
-        items.push_back(h);
+        if (hmv[k]) mitems.push_back(HllMvItem{h, start, int32_t(col.total_entries), 0});
+        else items.push_back(h);
         continue;
       }
       HllGroupItem gi{};
@@ -228,14 +246,32 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
         const GlobalDict& gd = P.gdicts[size_t(g)];
         if (!gd.identity && gd.remap[size_t(s)]) gi.g[g].remap = rdev.as<int32_t>() + roff[gd.remap[size_t(s)].get()];
       }
-      gitems.push_back(gi);
+      if (hmv[k]) mgitems.push_back(HllMvGroupItem{gi, start, int32_t(col.total_entries), 0});
+      else gitems.push_back(gi);
     }
   const size_t nitems = ng == 0 ? items.size() : gitems.size();
   const size_t isize = ng == 0 ? sizeof(HllItem) : sizeof(HllGroupItem);
   const void* ihost = ng == 0 ? static_cast<const void*>(items.data()) : static_cast<const void*>(gitems.data());
   DevBuf idev(ctx, std::max<size_t>(1, nitems) * isize);
   if (nitems) hip_check(hipMemcpyAsync(idev.p, ihost, nitems * isize, hipMemcpyHostToDevice, st), "HLL items H2D");
-  const int G = hll_wgs(ctx, max_words, nitems);
+  const size_t nmv = ng == 0 ? mitems.size() : mgitems.size();
+  const size_t msize = ng == 0 ? sizeof(HllMvItem) : sizeof(HllMvGroupItem);
+  const void* mhost = ng == 0 ? static_cast<const void*>(mitems.data()) : static_cast<const void*>(mgitems.data());
+  DevBuf mdev(ctx, std::max<size_t>(1, nmv) * msize);
+  if (nmv) hip_check(hipMemcpyAsync(mdev.p, mhost, nmv * msize, hipMemcpyHostToDevice, st), "HLL MV items H2D");
+  const int G = hll_wgs(ctx, max_words, nitems + nmv);
+  // the single-value and the multi-value items: one launch each, on the same stream, into their own register blocks
+  if (scanned && nmv) {
+    if (ng == 0) {
+      PGX_LAUNCH(st, "pgx_hll_offer_mv",
+                 pgx_launch_hll_offer_mv(mdev.as<HllMvItem>(), mitems.data(), int(nmv), G, st), "HLL MV offers");
+    } else {
+      PGX_LAUNCH(st, "pgx_hll_offer_mv_group",
+                 pgx_launch_hll_offer_mv_group(mdev.as<HllMvGroupItem>(), mgitems.data(), int(nmv), ng, K.gmul,
+                                               int64_t(slots), G, st),
+                 "HLL MV group offers");
+    }
+  }
   if (scanned && nitems) {
     if (ng == 0) {
       PGX_LAUNCH(st, "pgx_hll_offer", pgx_launch_hll_offer(idev.as<HllItem>(), items.data(), int(nitems), G, st),

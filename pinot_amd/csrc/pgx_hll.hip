@@ -21,6 +21,12 @@
 //                        whenever any of the four neighbours changed; the price is 4 bytes per register to zero and a
 //                        narrowing pass (pgx_hll_narrow) over the groups the result holds.
 //   pgx_hll_narrow       one thread per (group, four registers): the listed slots' registers as bytes.
+//   pgx_hll_offer_mv     DISTINCTCOUNTHLLMV (DistinctCountHLLMVAggregationFunction.java): the column is multi-value and
+//                        every value of every selected doc is offered.  The same grid and LDS registers; a run of
+//                        consecutive selected docs of a mask word owns one contiguous range of the value stream
+//                        (start[first] .. start[last + 1]), walked in passes of independent accesses.
+//   pgx_hll_offer_mv_group  the same into the slots x 256 table: the slot of a doc from its single-value group columns
+//                        as in pgx_hll_offer_group, every value of the doc into that slot.
 // No workgroup waits on another; all stores are plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
 
@@ -253,6 +259,154 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
   }
 }
 
+// ---- DISTINCTCOUNTHLLMV: every value of every selected doc ----------------------------------------------------------
+// Value rows lo .. lo + N - 1 of an item's value stream offered into regs (256 u32, LDS or HBM), in passes of N
+// independent accesses: the dictIds, the codes, the registers, then the few atomics.  lo < hi <= A.h.total: rows at or
+// past hi take row hi - 1's address and offer nothing (their mask is 0), so no load is conditional.  Masks, not
+// compares, across the loads (hll_gather_codes).  hll_value2 reads the row's dword and the next one: for a row below
+// `total` both lie inside the stream's allocation, because padded_fwd_bytes(total, bits) covers whole tiles of rows
+// and 64 bytes more (the second dword of the last row ends at most 8 bytes past total * bits / 8).
+template <int N>
+__device__ __forceinline__ void hll_mv_batch(uint32_t* regs, const HllItem& A, uint32_t lo, uint32_t hi) {
+  uint32_t v[N], m[N];
+  const uint32_t nc = static_cast<uint32_t>(A.ncodes);  // >= 1 (hll_words)
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const uint32_t r = lo + static_cast<uint32_t>(i);
+    const uint32_t on = static_cast<uint32_t>(static_cast<int32_t>(r - hi) >> 31);  // r < hi (both below 2^31 + N)
+    const uint32_t id = hll_value2(A.fwd, static_cast<int32_t>(__builtin_elementwise_min(r, hi - 1u)), A.bits);
+    const uint32_t t = __builtin_elementwise_min(id, nc), d = t - nc;  // d == 0: a dictId at or past the table
+    m[i] = static_cast<uint32_t>(static_cast<int32_t>(d | (0u - d)) >> 31) & on;
+    v[i] = t & m[i];
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = A.codes[v[i]] & m[i];  // (a code is never 0)
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = regs[v[i] >> 8] < (v[i] & 0xFFu) ? v[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    if (v[i] != 0u) atomicMax(&regs[v[i] >> 8], v[i] & 0xFFu);
+}
+
+constexpr int kHllMvBatch = 16;  // value rows per pass of a long range
+constexpr int kHllMvShort = 4;   // ... of a range's last rows (a sparse word's doc has a few values only)
+
+// value rows [lo, hi) clamped to the stream: start[] is device data nobody validated
+__device__ __forceinline__ void hll_mv_range(uint32_t* regs, const HllItem& A, int32_t total, int32_t lo, int32_t hi) {
+  uint32_t a = static_cast<uint32_t>(lo < 0 ? 0 : lo);
+  const uint32_t b = static_cast<uint32_t>(hi < 0 ? 0 : hi < total ? hi : total);  // total > 0 (hll_mv_words)
+  while (a < b && b - a > static_cast<uint32_t>(kHllMvShort)) {
+    hll_mv_batch<kHllMvBatch>(regs, A, a, b);
+    a += kHllMvBatch;
+  }
+  if (a < b) hll_mv_batch<kHllMvShort>(regs, A, a, b);
+}
+
+__device__ __forceinline__ int hll_mv_words(const HllItem& A, const int32_t* start, int32_t total) {
+  return start && total > 0 ? hll_words(A) : 0;
+}
+
+// A maximal run of selected docs a .. a + len - 1 of a mask word owns one contiguous value range: ranges are walked,
+// not docs, and a fully selected word is one range.  One lane walks a range alone (long ranges are not shared across
+// the wave), so a doc with hundreds of values keeps its lane busy while the wave's other lanes wait.
+__global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv(const HllMvItem* __restrict__ items, int nitems) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  __shared__ uint32_t regs[kHllRegs];
+  const int tid = static_cast<int>(threadIdx.x);
+  regs[tid] = 0u;
+  __syncthreads();
+  const HllMvItem M = items[item];
+  const HllItem A = M.h;
+  const int words = hll_mv_words(A, M.start, M.total);
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
+    const int32_t d0 = static_cast<int32_t>(w * 32);
+    for (uint32_t m = hll_mask_word(A, w); m;) {  // (bits at and past num_docs are off: d0 + a + len <= num_docs)
+      const int a = __builtin_ctz(m);
+      const uint32_t rest = ~(m >> a);
+      const int len = rest ? __builtin_ctz(rest) : 32;
+      m &= ~((len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u)) << a);
+      hll_mv_range(regs, A, M.total, M.start[d0 + a], M.start[d0 + a + len]);
+    }
+  }
+  __syncthreads();
+  const uint32_t r = regs[tid];
+  if (r != 0u && A.out[tid] < r) atomicMax(&A.out[tid], r);
+}
+
+constexpr uint32_t kHllNoSlot = 0x20000u;  // above every slot (kHllMaxGroupSlots = 0x10000)
+
+// One group column's global id folded into a doc's slot so far.  32-bit throughout: a slot inside the key space and
+// each of its terms are below 0x10000, so both are clamped there before they are added; an id of 65536 or more (a
+// remap entry of -1 among them) is outside every key space.  A result of 0x10000 or more stays there.
+__device__ __forceinline__ uint32_t hll_mv_fold(uint32_t prev, uint32_t gid, uint32_t mul) {
+  const uint32_t hi = gid >> 16;
+  const uint32_t bad = static_cast<uint32_t>(static_cast<int32_t>(hi | (0u - hi)) >> 31);
+  const uint32_t term = __builtin_elementwise_min((gid & 0xFFFFu) * mul, 0x10000u);  // mul <= 0x10000 (launcher)
+  return (__builtin_elementwise_min(prev, 0x10000u) + term) | (bad & kHllNoSlot);
+}
+
+// The same over a table of slots x 256 registers in HBM.  A doc's slot comes from its single-value group columns as in
+// pgx_hll_offer_group; every value of the doc goes to that slot, so ranges are walked per doc.  A word's slots are
+// computed first, for a dense word in passes of independent loads over its 32 docs (all inside the group columns'
+// padded indexes; a doc that is not selected takes remap entry 0), and parked in LDS: one column of 32 per thread,
+// which only that thread touches.
+__global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv_group(const HllMvGroupItem* __restrict__ items,
+                                                                    int nitems, const HllGroupKey K) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  __shared__ uint32_t slot_of[32 * kHllBlock];
+  const HllMvGroupItem& M = items[item];
+  const HllGroupItem& G = M.g;
+  const HllItem A = G.h;
+  const int32_t* __restrict__ start = M.start;
+  const int32_t total = M.total;
+  const int tid = static_cast<int>(threadIdx.x);
+  uint32_t* const mine = slot_of + tid;  // doc j of the word: mine[j * kHllBlock]
+  int words = hll_mv_words(A, start, total);
+  for (int g = 0; g < K.ngcols; ++g)
+    if (G.g[g].bits < 1 || G.g[g].bits > 32) words = 0;
+  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
+    const uint32_t sel = hll_mask_word(A, w);
+    if (sel == 0u) continue;
+    const int32_t d0 = static_cast<int32_t>(w * 32);
+    const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
+    for (int g = 0; g < K.ngcols; ++g) {
+      const uint32_t* __restrict__ gf = G.g[g].fwd;
+      const int32_t* __restrict__ rm = G.g[g].remap;
+      const int gb = G.g[g].bits;
+      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+      if (dense) {
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j) {
+          const uint32_t on = 0u - ((sel >> j) & 1u);
+          const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
+          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
+          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+        }
+      } else {
+        for (uint32_t m = sel; m;) {
+          const int j = __builtin_ctz(m);
+          m &= m - 1u;
+          const uint32_t id = hll_value(gf, d0 + j, gb);
+          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
+          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+        }
+      }
+    }
+    for (uint32_t m = sel; m;) {
+      const int j = __builtin_ctz(m);
+      m &= m - 1u;
+      const uint32_t s = mine[j * kHllBlock];
+      if (s >= slots32) continue;  // (a key outside the planned space: the doc offers nothing)
+      hll_mv_range(A.out + static_cast<size_t>(s) * kHllRegs, A, total, start[d0 + j], start[d0 + j + 1]);
+    }
+  }
+}
+
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_narrow(const uint32_t* __restrict__ table,
                                                             const int64_t* __restrict__ slot, int64_t ngroups,
                                                             uint64_t slots, uint32_t* __restrict__ out) {
@@ -322,5 +476,46 @@ extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t
   const int64_t blocks = (ngroups * (pgx::kHllRegs / 4) + pgx::kHllBlock - 1) / pgx::kHllBlock;
   hipLaunchKernelGGL(pgx::pgx_hll_narrow, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kHllBlock), 0, stream, table,
                      slot, ngroups, static_cast<uint64_t>(slots), out);
+  return hipGetLastError();
+}
+
+// DISTINCTCOUNTHLLMV.  Validated like the launchers above, on the caller's host copy of the items; the start array
+// itself is device data, so the kernels clamp every value range to `total`.
+extern "C" hipError_t pgx_launch_hll_offer_mv(const pgx::HllMvItem* items, const pgx::HllMvItem* check, int nitems,
+                                              int wgs_per_item, hipStream_t stream) {
+  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < nitems; ++i)
+    if (!hll_item_ok(check[i].h) || !check[i].start || check[i].total < 0) return hipErrorInvalidValue;
+  if (nitems == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_hll_offer_mv, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
+                     dim3(pgx::kHllBlock), 0, stream, items, nitems);
+  return hipGetLastError();
+}
+
+// Every item's `g.h.out` is a table of slots x 256 u32 registers, zeroed by the caller.  gmul: ngcols host values.
+extern "C" hipError_t pgx_launch_hll_offer_mv_group(const pgx::HllMvGroupItem* items,
+                                                    const pgx::HllMvGroupItem* check, int nitems, int ngcols,
+                                                    const uint64_t* gmul, int64_t slots, int wgs_per_item,
+                                                    hipStream_t stream) {
+  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check || !gmul)
+    return hipErrorInvalidValue;
+  if (ngcols < 1 || ngcols > pgx::kMaxGroupCols || slots < 1 || slots > pgx::kHllMaxGroupSlots)
+    return hipErrorInvalidValue;
+  for (int g = 0; g < ngcols; ++g)
+    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return hipErrorInvalidValue;  // a mixed-radix layout
+  for (int i = 0; i < nitems; ++i) {
+    if (!hll_item_ok(check[i].g.h) || !check[i].start || check[i].total < 0) return hipErrorInvalidValue;
+    for (int g = 0; g < ngcols; ++g)
+      if (!check[i].g.g[g].fwd || check[i].g.g[g].bits < 1 || check[i].g.g[g].bits > 32) return hipErrorInvalidValue;
+  }
+  if (nitems == 0) return hipSuccess;
+  pgx::HllGroupKey K{};
+  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
+  K.slots = static_cast<uint64_t>(slots);
+  K.ngcols = ngcols;
+  hipLaunchKernelGGL(pgx::pgx_hll_offer_mv_group,
+                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kHllBlock), 0,
+                     stream, items, nitems, K);
   return hipGetLastError();
 }

@@ -1471,7 +1471,7 @@ void run_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n
   for (const auto& g : q.group_cols)
     for (int s = 0; s < n && !mv_group; ++s) mv_group = segs[s]->col(g).is_mv;
   bool mv_fn = false;
-  for (int fn : q.agg_fn) mv_fn = mv_fn || fn >= PGX_COUNTMV;
+  for (int fn : q.agg_fn) mv_fn = mv_fn || is_standard_mv_fn(fn);
   if (mv_group || (mv_fn && !q.group_cols.empty())) {
     // across devices the keys come from the shared Domain and the partials merge by key on the host (run_multi,
     // merge_host_groups); a caller-owned dense table is not offered (pgx_query_dense_slots reports -1)
@@ -1571,6 +1571,15 @@ void run_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n
   if (cache && plan_cacheable(P)) plan_cache_insert(&q, ctx, segs, n, std::move(uids), pkey, std::move(Pp), std::move(Bp));
 }
 
+void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign) {
+  std::lock_guard<std::mutex> g(ctx->kinds_mu);
+  for (const StagedColumn& c : seg.cols) {
+    auto& k = ctx->col_kinds[c.name];
+    (c.is_mv ? k.second : k.first) += sign;
+    if (k.first <= 0 && k.second <= 0) ctx->col_kinds.erase(c.name);
+  }
+}
+
 }  // namespace pgxh
 
 void pgx_result::ready() const {
@@ -1656,6 +1665,7 @@ pgx_status pgx_segment_stage(pgx_ctx* ctx, const pgx_segment_desc* d, pgx_segmen
       parse_star_tree(*seg);
     }
     ctx->refs.fetch_add(1);  // released by pgx_segment_release
+    ctx_count_columns(ctx, *seg, +1);
     *out = seg.release();
   });
 }
@@ -1664,6 +1674,7 @@ pgx_status pgx_segment_release(pgx_segment* seg) {
   return guarded([&] {
     if (!seg) return;
     pgx_ctx* ctx = seg->ctx;
+    if (ctx) ctx_count_columns(ctx, *seg, -1);
     delete seg;
     g_segment_frees.fetch_add(1);
     if (ctx) ctx_unref(ctx);
@@ -1683,11 +1694,17 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* d, pgx_query** 
     auto q = std::make_unique<pgx_query>();
     for (int a = 0; a < d->num_aggs; ++a) {
       const int fn = d->aggs[a].fn;
-      if (fn < PGX_COUNT || fn > PGX_DISTINCTCOUNTHLL) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
+      if (fn < PGX_COUNT || fn > PGX_DISTINCTCOUNTHLLMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
       q->agg_fn.push_back(fn);
       const char* c = d->aggs[a].column;
       std::string col = (c && std::strcmp(c, "*") != 0) ? c : "";
       if (fn != PGX_COUNT && col.empty()) fail(PGX_ERR_INVALID_ARG, "aggregation without column");
+      if (fn == PGX_DISTINCTCOUNTHLLMV) {  // known already: the column is single-value wherever it is staged
+        std::lock_guard<std::mutex> g(ctx->kinds_mu);
+        auto it = ctx->col_kinds.find(col);
+        if (it != ctx->col_kinds.end() && it->second.first > 0 && it->second.second == 0)
+          fail(PGX_ERR_UNSUPPORTED, "multi-value function on single-value column " + col);
+      }
       q->agg_col.push_back(fn == PGX_COUNT ? "" : col);
     }
     for (int g = 0; g < d->num_group_cols; ++g) q->group_cols.push_back(d->group_cols[g]);

@@ -128,6 +128,12 @@ extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx:
 extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
                                                  int nitems, int ngcols, const uint64_t* gmul, int64_t slots,
                                                  int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer_mv(const pgx::HllMvItem* items, const pgx::HllMvItem* check, int nitems,
+                                              int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer_mv_group(const pgx::HllMvGroupItem* items,
+                                                    const pgx::HllMvGroupItem* check, int nitems, int ngcols,
+                                                    const uint64_t* gmul, int64_t slots, int wgs_per_item,
+                                                    hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t* slot, int64_t ngroups, int64_t slots,
                                             uint32_t* out, hipStream_t stream);
 struct pgx_ctx;
@@ -368,6 +374,11 @@ struct pgx_ctx {
   // domains, so thousands of segments then read one L2-resident table instead of thousands of private copies.
   std::mutex dict_mu;
   std::unordered_map<uint64_t, std::weak_ptr<SharedDict>> dicts;
+  // Per column name: how many staged segments hold it single-value / multi-value (ctx_count_columns).
+  // pgx_query_compile has no segments to look at; with this it refuses a DISTINCTCOUNTHLLMV whose column every staged
+  // segment holds single-value, which run_hll would refuse at every execution over them.
+  std::mutex kinds_mu;
+  std::unordered_map<std::string, std::pair<int, int>> col_kinds;
   WorkerPool pool;           // started lazily (first large query)
   std::once_flag pool_once;
   TaskTeam plan_team;        // batched plans (run_batched), started lazily
@@ -1122,8 +1133,15 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
 
 void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
              const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom);  // pgx_hll.cpp
+// COUNTMV .. AVGMV (run_mv / run_mv_group).  The HLL codes lie above them and are not meant: a query with one is
+// dispatched to run_hll before any of these tests is reached.
+inline bool is_standard_mv_fn(int fn) { return fn >= PGX_COUNTMV && fn <= PGX_AVGMV; }
+// A segment was staged (sign +1) or is being released (-1): its columns in ctx->col_kinds.
+void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign);
 inline bool query_has_hll(const pgx_query& q) {
-  return std::find(q.agg_fn.begin(), q.agg_fn.end(), int(PGX_DISTINCTCOUNTHLL)) != q.agg_fn.end();
+  for (int fn : q.agg_fn)
+    if (fn == PGX_DISTINCTCOUNTHLL || fn == PGX_DISTINCTCOUNTHLLMV) return true;
+  return false;
 }
 
 void parse_star_tree(pgx_segment& seg);

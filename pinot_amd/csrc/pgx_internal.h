@@ -166,6 +166,23 @@ struct HllGroupItem {
   HllGCol g[kMaxGroupCols];
 };
 static_assert(sizeof(HllItem) == 48 && sizeof(HllGroupItem) == 48 + kMaxGroupCols * 24, "tests/hll_ref.py mirrors these");
+// DISTINCTCOUNTHLLMV: the item's column is multi-value.  h.fwd is the value stream (`total` rows of h.bits bits,
+// padded as a forward index of `total` rows), h.sel and h.num_docs count docs, and doc d owns the value rows
+// start[d] .. start[d + 1] - 1.  The group columns of the group form are single-value (one row per doc).
+struct HllMvItem {
+  HllItem h;
+  const int32_t* start;        // num_docs + 1 ascending entries; entries past index num_docs are never read
+  int32_t total;               // value rows of the stream: rows at or past it are never read, whatever start[] holds
+  int32_t pad;
+};
+struct HllMvGroupItem {
+  HllGroupItem g;
+  const int32_t* start;
+  int32_t total;
+  int32_t pad;
+};
+static_assert(sizeof(HllMvItem) == 64 && sizeof(HllMvGroupItem) == sizeof(HllGroupItem) + 16,
+              "tests/hll_mv_ref.py mirrors these");
 struct HllGroupKey {           // passed by value: slot = sum over the group columns of global id x gmul
   uint64_t gmul[kMaxGroupCols];
   uint64_t slots;

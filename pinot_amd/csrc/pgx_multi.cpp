@@ -75,7 +75,7 @@ void merge_device_groups(pgx_ctx* ctx, hipStream_t st, const uint64_t* keys, con
 // A multi-value group column, or a multi-value function (run_mv / run_mv_group execute these).
 bool query_is_mv(const pgx_query& q, pgx_segment* const* segs, int n) {
   for (int fn : q.agg_fn)
-    if (fn >= PGX_COUNTMV) return true;
+    if (is_standard_mv_fn(fn)) return true;
   for (const auto& g : q.group_cols)
     for (int s = 0; s < n; ++s)
       if (segs[s]->col(g).is_mv) return true;

@@ -19,7 +19,7 @@ void run_mv(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, c
   std::vector<int> sv_pos(q.agg_fn.size(), -1), mv_pos(q.agg_fn.size(), -1);
   std::vector<std::string> mv_cols;
   for (size_t a = 0; a < q.agg_fn.size(); ++a) {
-    if (q.agg_fn[a] >= PGX_COUNTMV) {
+    if (is_standard_mv_fn(q.agg_fn[a])) {
       const std::string& c = q.agg_col[a];
       for (int s = 0; s < n; ++s) {
         const StagedColumn& col = segs[s]->col(c);
@@ -142,7 +142,8 @@ void run_mv_group(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, in
     const int f = q.agg_fn[a];
     mvf[a] = int8_t(f);  // pgx_agg_fn and MvFnKind share their numbering
     if (f == PGX_COUNT) continue;
-    const bool mvfn = f >= PGX_COUNTMV;
+    if (f > PGX_AVGMV) fail(PGX_ERR_INTERNAL, "HLL function in the multi-value group-by");
+    const bool mvfn = is_standard_mv_fn(f);
     for (int s = 0; s < n; ++s) {
       const StagedColumn& c = segs[s]->col(q.agg_col[a]);
       if (c.is_mv != mvfn)

@@ -896,7 +896,7 @@ void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
     }
     const StagedColumn& c = segs[0]->col(q.agg_col[a]);
     if (c.data_type == PGX_STRING) fail(PGX_ERR_UNSUPPORTED, "numeric aggregation on STRING column " + c.name);
-    if (fn >= PGX_COUNTMV) fail(PGX_ERR_INTERNAL, "multi-value function in the single-value plan");
+    if (fn > PGX_AVG) fail(PGX_ERR_INTERNAL, "multi-value or HLL function in the single-value plan");
     for (int s = 0; s < n; ++s)
       if (segs[s]->col(q.agg_col[a]).is_mv)
         fail(PGX_ERR_UNSUPPORTED, "single-value aggregation on multi-value column " + c.name);

@@ -207,6 +207,7 @@ pgx_status pgx_mutable_snapshot(pgx_mutable* m, pgx_segment** out) {
     }
     hip_check(hipStreamSynchronize(st), "sync");
     ctx->refs.fetch_add(1);  // released by pgx_segment_release
+    ctx_count_columns(ctx, *seg, +1);
     *out = seg.release();
   });
 }

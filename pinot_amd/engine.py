@@ -29,7 +29,8 @@ from .segment import Column, SegmentData
 _DT = {"INT": N.PGX_INT, "LONG": N.PGX_LONG, "FLOAT": N.PGX_FLOAT, "DOUBLE": N.PGX_DOUBLE, "STRING": N.PGX_STRING}
 _FN = {"count": N.PGX_COUNT, "sum": N.PGX_SUM, "min": N.PGX_MIN, "max": N.PGX_MAX, "avg": N.PGX_AVG,
        "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV,
-       "distinctcounthll": N.PGX_DISTINCTCOUNTHLL}
+       "distinctcounthll": N.PGX_DISTINCTCOUNTHLL, "distinctcounthllmv": N.PGX_DISTINCTCOUNTHLLMV}
+_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # their intermediates are register sets (pgx_result_hll)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -731,7 +732,7 @@ def render_key(q: _Query, segments: Sequence[IndexSegment], g: int, seg_index: i
 
 
 def result_hll(r, fn_index: int, first_group: int = 0, num_groups: int = 1) -> np.ndarray:
-    """pgx_result_hll: the HyperLogLog registers of a DISTINCTCOUNTHLL function, uint8 [num_groups, 256] (one "group"
+    """pgx_result_hll: the HyperLogLog registers of a DISTINCTCOUNTHLL[MV] function, uint8 [num_groups, 256] (one "group"
     for an aggregation-only result)."""
     regs = np.zeros((max(num_groups, 1), 256), dtype=np.uint8)
     N.check(N.lib().pgx_result_hll(r, fn_index, first_group, num_groups, regs.ctypes.data))
@@ -746,7 +747,7 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if not q.group_cols:
         out = []
         for i, fn in enumerate(q.fns):
-            if fn == "distinctcounthll":  # the intermediate is the register set (hll.py)
+            if fn in _HLL_FNS:  # the intermediate is the register set (hll.py)
                 out.append(result_hll(r, i)[0])
                 continue
             v, c = C.c_double(), C.c_int64()
@@ -775,7 +776,7 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     keys = ["\t".join(p[i] for p in key_parts) for i in range(n)]
     vals = []
     for i, fn in enumerate(q.fns):
-        if fn == "distinctcounthll":
+        if fn in _HLL_FNS:
             vals.append(list(result_hll(r, i, 0, n)))
             continue
         v = np.zeros(max(n, 1), dtype=np.float64)
@@ -793,7 +794,7 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if trim:
         trimmed = []
         for i in range(len(q.fns)):
-            if q.fns[i] == "distinctcounthll":  # no order to trim by: every group (pgx_result_trim refuses the index)
+            if q.fns[i] in _HLL_FNS:  # no order to trim by: every group (pgx_result_trim refuses the index)
                 trimmed.append({keys[j]: per_group[j][i] for j in range(n)})
                 continue
             cap = C.c_int64(n)

@@ -11,8 +11,8 @@ decomposed on the host into GPU sub-queries the fused scan kernels already run:
 * PERCENTILEnn(c) -> the same ``GROUP BY c`` histogram; intermediate the (value, count) pairs in value order, i.e. the
   reference's DoubleArrayList of every selected value (PercentileAggregationFunction.java aggregate) held as a multiset;
 * DISTINCTCOUNTHLL(c) -> a function of the base query itself (PGX_DISTINCTCOUNTHLL: the registers are built on the
-  device and read with pgx_result_hll; ``native_hll``).  Where the library refuses the shape, or with PGX_HLL_NATIVE=0,
-  the same histogram; intermediate the HyperLogLog registers of the distinct hash codes (operator/aggregation/function/
+  device and read with pgx_result_hll; ``native_hll``), and DISTINCTCOUNTHLLMV(c) likewise (PGX_DISTINCTCOUNTHLLMV:
+  every value of every selected doc).  Where the library refuses the shape, or with PGX_HLL_NATIVE=0, the same histogram; intermediate the HyperLogLog registers of the distinct hash codes (operator/aggregation/function/
   DistinctCountHLLAggregationFunction.java aggregate: hll.offer((int) hash)), which depend only on that set (hll.py).
 
 One histogram sub-query serves every DISTINCTCOUNT / PERCENTILE over the same column.  Statistics are the base query's,
@@ -37,6 +37,7 @@ from .pql import EXT_FUNCTIONS, EXT_MV_FUNCTIONS
 
 
 _HIST_FNS = ("distinctcount", "distinctcounthll", "fasthll")
+_NATIVE_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # functions of the base query when `native_hll`
 
 
 def base_fn(fn: str) -> str:
@@ -133,13 +134,13 @@ def _projection_count(request: dict) -> int:
 
 
 def native_hll(request: dict, segments) -> bool:
-    """Whether the request's single-value DISTINCTCOUNTHLL functions run inside the base query (PGX_DISTINCTCOUNTHLL:
-    registers computed on the device, pgx_hll.hip) instead of through the ``GROUP BY c`` histogram.  PGX_HLL_NATIVE=0
+    """Whether the request's DISTINCTCOUNTHLL and DISTINCTCOUNTHLLMV functions run inside the base query
+    (PGX_DISTINCTCOUNTHLL / PGX_DISTINCTCOUNTHLLMV: registers computed on the device, pgx_hll.hip) instead of through the ``GROUP BY c`` histogram.  PGX_HLL_NATIVE=0
     forces the histogram (A/B, tests).  The native query never uses a star tree (every raw row is offered), so a request
     whose base query a star tree could answer keeps the decomposition, and with it its statistics."""
     if os.environ.get("PGX_HLL_NATIVE", "1") == "0":
         return False
-    if not any(a["fn"] == "distinctcounthll" for a in request["aggregations"]):
+    if not any(a["fn"] in _NATIVE_HLL_FNS for a in request["aggregations"]):
         return False
     use_st = str((request.get("debug_options") or {}).get("useStarTree", "true")).lower() != "false"
     return not (use_st and any(getattr(s.data, "star_tree", None) is not None for s in segments))
@@ -147,13 +148,13 @@ def native_hll(request: dict, segments) -> bool:
 
 def _base_request(request: dict, native: bool = False):
     """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE; with `native` the
-    DISTINCTCOUNTHLL functions as well) and, per original function, its base slot: an index, a (min, max) index pair,
+    DISTINCTCOUNTHLL and DISTINCTCOUNTHLLMV functions as well) and, per original function, its base slot: an index, a (min, max) index pair,
     or None (histogram functions)."""
     base = [{"fn": "count", "column": "*"}]
     slot = []
     for a in request["aggregations"]:
         fn = a["fn"]
-        if native and fn == "distinctcounthll":
+        if native and fn in _NATIVE_HLL_FNS:
             base.append(dict(a))
             slot.append(len(base) - 1)
         elif fn == "minmaxrange":
@@ -176,7 +177,7 @@ def _hist_columns(request: dict, segments, native: bool = False) -> List[str]:
     for a in request["aggregations"]:
         mv = a["fn"] in EXT_MV_FUNCTIONS
         fn = base_fn(a["fn"])
-        if native and a["fn"] == "distinctcounthll":  # in the base query: no histogram on its account
+        if native and a["fn"] in _NATIVE_HLL_FNS:  # in the base query: no histogram on its account
             continue
         if fn not in _HIST_FNS and fn != "minmaxrange" and not fn.startswith("percentile"):
             continue

@@ -20,6 +20,7 @@ class PgxError(RuntimeError):
 PGX_INT, PGX_LONG, PGX_FLOAT, PGX_DOUBLE, PGX_STRING = range(5)
 PGX_COUNT, PGX_SUM, PGX_MIN, PGX_MAX, PGX_AVG, PGX_COUNTMV, PGX_SUMMV, PGX_MINMV, PGX_MAXMV, PGX_AVGMV = range(10)
 PGX_DISTINCTCOUNTHLL = 10
+PGX_DISTINCTCOUNTHLLMV = 11
 PGX_HLL_MAX_GROUP_SLOTS = 65536
 PGX_PRED = {"EQ": 0, "NEQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 PGX_F_LEAF, PGX_F_AND, PGX_F_OR = 0, 1, 2

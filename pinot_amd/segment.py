@@ -356,8 +356,16 @@ def make_mv_column(name: str, doc_values: Sequence[Sequence], data_type: str = "
                    inverted: bool = False) -> Column:
     """A v1 multi-value column from per-doc value lists (SegmentDictionaryCreator over all values; MV forward index;
     the inverted index holds every doc under each of its values, HeapBitmapInvertedIndexCreator.add(int, int[]))."""
-    flat = np.concatenate([np.asarray(v) for v in doc_values])
-    dictionary, ids = np.unique(flat.astype(_DICT_NP[data_type].replace(">", "<")), return_inverse=True)
+    if data_type == "STRING":  # the dictionary as make_column builds it: the padded strings in Java order
+        sv = [x.decode() if isinstance(x, bytes) else str(x) for v in doc_values for x in np.asarray(v).tolist()]
+        distinct = list(set(sv))
+        width = max([1] + [len(x.encode("utf-8")) for x in distinct])
+        dictionary = _java_string_sort(distinct, width, DEFAULT_PAD)
+        lookup = {v: i for i, v in enumerate(dictionary)}
+        ids = np.array([lookup[v] for v in sv], dtype=np.int64)
+    else:
+        flat = np.concatenate([np.asarray(v) for v in doc_values])
+        dictionary, ids = np.unique(flat.astype(_DICT_NP[data_type].replace(">", "<")), return_inverse=True)
     card = len(dictionary)
     bits = num_bits(card)
     lens = [len(v) for v in doc_values]
@@ -371,8 +379,12 @@ def make_mv_column(name: str, doc_values: Sequence[Sequence], data_type: str = "
         blobs = [roaring_serialize(p) for p in per]
         offs = np.concatenate([[0], np.cumsum([len(b) for b in blobs])]) + 4 * (card + 1)
         inv = offs.astype(">i4").tobytes() + b"".join(blobs)
-    width = int(_DICT_NP[data_type][-1])
-    dict_bytes = np.asarray(dictionary).astype(_DICT_NP[data_type]).tobytes()
+    if data_type == "STRING":
+        dict_bytes = b"".join(x.encode("utf-8") + DEFAULT_PAD.encode() * (width - len(x.encode("utf-8")))
+                              for x in dictionary)
+    else:
+        width = int(_DICT_NP[data_type][-1])
+        dict_bytes = np.asarray(dictionary).astype(_DICT_NP[data_type]).tobytes()
     n = len(doc_values)
     return Column(name, data_type, column_type, card, bits, n, n, False, inverted, dict_bytes, width, fwd, None, inv,
                   DEFAULT_PAD, True, int(starts[-1]), int(max(lens)))
