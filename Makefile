@@ -17,7 +17,7 @@ build/pgx_host.o: $(CSRC)/pgx_host.cpp $(HOST_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_select.o build/pgx_hll.o build/pgx_plan_cache.o build/pgx_plan.o: build/%.o: $(CSRC)/%.cpp $(HOST_HDR)
+build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_select.o build/pgx_hll.o build/pgx_distinct.o build/pgx_plan_cache.o build/pgx_plan.o: build/%.o: $(CSRC)/%.cpp $(HOST_HDR) $(CSRC)/pgx_hash.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -48,14 +48,24 @@ build/pgx_select_hip.o: $(CSRC)/pgx_select.hip $(CSRC)/pgx_internal.h $(CSRC)/pg
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o
+build/pgx_distinct_hip.o: $(CSRC)/pgx_distinct.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o build/pgx_distinct_hip.o build/pgx_distinct.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ -L/opt/rocm/lib -lhiprtc -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
+
+# Host-only check of pgx_hash.h (the Java hash codes, the sort + unique union) under AddressSanitizer and UBSan: no device
+host-check: tests/host/distinct_host_check.cpp $(CSRC)/pgx_hash.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/distinct_host_check
+	build/distinct_host_check
 
 clean:
 	rm -rf build pinot_amd/libpgx.so
 
-.PHONY: all clean
+.PHONY: all clean host-check

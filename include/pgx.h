@@ -40,7 +40,8 @@ extern "C" {
 #define PGX_ABI_VERSION 8  /* 7: pgx_mutable_* (realtime segments in place); 8: pgx_result_record_words, records of
                               * every device-resident layout (several value columns, f64 sums); pgx_select_compile and
                               * pgx_result_select_* were added under 8: new entry points only, no existing struct or
-                              * call changed; likewise PGX_DISTINCTCOUNTHLL[MV], pgx_result_hll and pgx_hll_codes */
+                              * call changed; likewise PGX_DISTINCTCOUNTHLL[MV], pgx_result_hll and pgx_hll_codes, and
+                              * PGX_DISTINCTCOUNT[MV], pgx_result_distinct[_counts] and pgx_java_hash_codes */
 
 typedef enum {
   PGX_OK = 0,
@@ -59,10 +60,14 @@ typedef enum { PGX_INT = 0, PGX_LONG = 1, PGX_FLOAT = 2, PGX_DOUBLE = 3, PGX_STR
 /* PGX_DISTINCTCOUNTHLL (operator/aggregation/function/DistinctCountHLLAggregationFunction.java): a single-value
  * column of any of the five data types; its intermediate is 256 HyperLogLog registers per result (per group), read
  * with pgx_result_hll (below, "DISTINCTCOUNTHLL").  PGX_DISTINCTCOUNTHLLMV (DistinctCountHLLMVAggregationFunction.java)
- * is the same over every value of a multi-value column in the selected docs. */
+ * is the same over every value of a multi-value column in the selected docs.
+ * PGX_DISTINCTCOUNT (DistinctCountAggregationFunction.java) and PGX_DISTINCTCOUNTMV (DistinctCountMVAggregationFunction
+ * .java) are the exact forms: the intermediate is the set of those hash codes, read with pgx_result_distinct_counts and
+ * pgx_result_distinct (below, "DISTINCTCOUNT"). */
 typedef enum { PGX_COUNT = 0, PGX_SUM = 1, PGX_MIN = 2, PGX_MAX = 3, PGX_AVG = 4,
                PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9,
-               PGX_DISTINCTCOUNTHLL = 10, PGX_DISTINCTCOUNTHLLMV = 11 } pgx_agg_fn;
+               PGX_DISTINCTCOUNTHLL = 10, PGX_DISTINCTCOUNTHLLMV = 11,
+               PGX_DISTINCTCOUNT = 12, PGX_DISTINCTCOUNTMV = 13 } pgx_agg_fn;
 
 /* Predicate kinds (common/Predicate.java Type); they select the physical filter operator exactly as
  * plan/FilterPlanNode.java:118-132 does and drive the numEntriesScannedInFilter statistic. */
@@ -405,6 +410,38 @@ pgx_status pgx_result_hll(const pgx_result* r, int32_t agg_index, int64_t first_
  * x, register x >>> 24, rank numberOfLeadingZeros((x << 8) | 0x81) + 1 (1..25). */
 pgx_status pgx_hll_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
                          uint16_t* codes);
+
+/* ---- DISTINCTCOUNT ------------------------------------------------------------------------------
+ * PGX_DISTINCTCOUNT takes a single-value column of any of the five data types, PGX_DISTINCTCOUNTMV a multi-value one
+ * (every value of every selected doc).  The intermediate is the set of (int) hashCode(value), hashCode as described at
+ * pgx_java_hash_codes: two different values with equal hash codes count once (LONG 0 and 0x0000000100000001 both hash
+ * to 0).  The functions mix with the PGX_DISTINCTCOUNTHLL[MV] and the standard single-value functions in any order and
+ * run in the same scan; two of them over one column share their state; statistics are those of the HLL forms, and a
+ * column that an HLL and a DISTINCTCOUNT function both name counts once among the projected ones.
+ * pgx_result_distinct_counts writes the set size of groups first_group .. first_group + num_groups - 1, in the order
+ * of pgx_result_group_keys (an aggregation-only result has exactly one group).  pgx_result_distinct writes those groups'
+ * hash codes back to back, ascending and unique within each group; group i's codes start at the sum of the preceding
+ * counts.  PGX_ERR_INVALID_ARG: agg_index is not a PGX_DISTINCTCOUNT[MV] function (an HLL index among them), the range
+ * lies outside the result, or `capacity` (in codes) is smaller than the sum of the counts.  pgx_result_hll refuses a
+ * DISTINCTCOUNT index; pgx_result_agg, _group_values and _trim refuse it as they refuse an HLL index, and
+ * pgx_result_gather puts value 0 and count 0 there.
+ * pgx_query_compile returns PGX_ERR_UNSUPPORTED for PGX_DISTINCTCOUNTMV when every staged segment of the context that
+ * holds the column holds it single-value, and for PGX_DISTINCTCOUNT when every one holds it multi-value; a column no
+ * staged segment has compiles, and the execution checks its own segments ("DISTINCTCOUNT on multi-value column",
+ * "multi-value function on single-value column").
+ * PGX_ERR_UNSUPPORTED (the caller falls back): every limit of the HLL forms above, and presence bitmaps -- one bit per
+ * dictId, per group slot and per distinct dictionary of the executed segments -- of more than
+ * PGX_DISTINCT_MAX_TABLE_BYTES in all. */
+#define PGX_DISTINCT_MAX_TABLE_BYTES (256u << 20)
+pgx_status pgx_result_distinct_counts(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
+                                      int64_t* counts);
+pgx_status pgx_result_distinct(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
+                               int32_t* hash_codes, int64_t capacity);
+/* Host only, no device needed: hash_codes[i] = (int) hashCode of value i, the boxed Java value's: Integer the value,
+ * Long (int)(v ^ v >>> 32), Float floatToIntBits, Double (int)(bits ^ bits >>> 32), String 31 * h + unit over the
+ * UTF-16 code units.  Arguments and checks as for pgx_hll_codes. */
+pgx_status pgx_java_hash_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
+                               int32_t* hash_codes);
 
 /* Dense-table layout for PGX_X_KEEP_DENSE_ON_DEVICE (multi-GPU RCCL merge):
  * slots = product of group cardinalities; buffer = (1 + num_aggs) planes of slots x 8 bytes.

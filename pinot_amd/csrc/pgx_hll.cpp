@@ -3,6 +3,7 @@
 // offers (int) hashCode of every selected doc's value to a stream-lib HyperLogLog(log2m = 8); the executor hands it
 // DataFetcher.getSVHashCodeArray (common/DataFetcher.java:242-248: dictionary.get(dictId).hashCode()).  The kernels
 // are in pgx_hll.hip.  Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
+#include "pgx_hash.h"
 #include "pgx_host.h"
 
 namespace pgxh {
@@ -30,47 +31,14 @@ static uint16_t hll_code(int32_t hash_code) {
   return uint16_t(((x >> 24) << 8) | uint32_t(__builtin_clz(w) + 1));
 }
 
-static int32_t hash_long(int64_t v) { return int32_t(uint32_t(uint64_t(v) ^ (uint64_t(v) >> 32))); }
-static int32_t hash_float(float f) {  // Float.hashCode: floatToIntBits (NaN canonical)
-  if (f != f) return 0x7FC00000;
-  int32_t b;
-  std::memcpy(&b, &f, 4);
-  return b;
-}
-static int32_t hash_double(double d) {  // Double.hashCode: (int)(bits ^ bits >>> 32) of doubleToLongBits
-  uint64_t b = 0x7FF8000000000000ull;
-  if (d == d) std::memcpy(&b, &d, 8);
-  return int32_t(uint32_t(b ^ (b >> 32)));
-}
-// String.hashCode over the UTF-16 code units of a UTF-8 string (a malformed byte decodes to U+FFFD)
-static int32_t hash_utf8(const uint8_t* s, size_t n) {
-  uint32_t h = 0;
-  for (size_t i = 0; i < n;) {
-    uint32_t cp = 0xFFFDu;
-    const uint8_t b = s[i];
-    int more = b < 0x80 ? 0 : (b >> 5) == 6 ? 1 : (b >> 4) == 14 ? 2 : (b >> 3) == 30 ? 3 : -1;
-    if (more >= 0 && i + size_t(more) < n) {
-      uint32_t x = more == 0 ? b : more == 1 ? (b & 0x1Fu) : more == 2 ? (b & 0x0Fu) : (b & 0x07u);
-      bool ok = true;
-      for (int k = 1; k <= more; ++k) {
-        ok = ok && (s[i + k] >> 6) == 2;
-        x = (x << 6) | (s[i + k] & 0x3Fu);
-      }
-      if (ok && x <= 0x10FFFFu) {
-        cp = x;
-        i += size_t(more);
-      }
-    }
-    ++i;
-    if (cp >= 0x10000u) {  // a surrogate pair
-      cp -= 0x10000u;
-      h = 31u * h + (0xD800u + (cp >> 10));
-      h = 31u * h + (0xDC00u + (cp & 0x3FFu));
-    } else {
-      h = 31u * h + cp;
-    }
+static int32_t dict_hash_code(const StagedColumn& c, int i) {
+  switch (c.data_type) {
+    case PGX_INT: return int32_t(c.ivals[size_t(i)]);
+    case PGX_LONG: return hash_long(c.ivals[size_t(i)]);
+    case PGX_FLOAT: return hash_float(float(c.dvals[size_t(i)]));
+    case PGX_DOUBLE: return hash_double(c.dvals[size_t(i)]);
+    default: return hash_utf8(reinterpret_cast<const uint8_t*>(c.svals[size_t(i)].data()), c.svals[size_t(i)].size());
   }
-  return int32_t(h);
 }
 
 // The column's code table in HBM, built on the first query that names it.  Numeric dictionaries share it through
@@ -81,23 +49,24 @@ static const uint16_t* hll_code_table(pgx_ctx* ctx, const StagedColumn& c) {
   DevBuf& buf = c.shared ? c.shared->hll_codes : c.hll_codes;
   if (buf.p) return buf.as<uint16_t>();
   std::vector<uint16_t> codes(size_t(std::max(c.card, 1)), 0);
-  for (int i = 0; i < c.card; ++i) {
-    int32_t h;
-    switch (c.data_type) {
-      case PGX_INT: h = int32_t(c.ivals[size_t(i)]); break;
-      case PGX_LONG: h = hash_long(c.ivals[size_t(i)]); break;
-      case PGX_FLOAT: h = hash_float(float(c.dvals[size_t(i)])); break;
-      case PGX_DOUBLE: h = hash_double(c.dvals[size_t(i)]); break;
-      default:
-        h = hash_utf8(reinterpret_cast<const uint8_t*>(c.svals[size_t(i)].data()), c.svals[size_t(i)].size());
-        break;
-    }
-    codes[size_t(i)] = hll_code(h);
-  }
+  for (int i = 0; i < c.card; ++i) codes[size_t(i)] = hll_code(dict_hash_code(c, i));
   DevBuf b(ctx, codes.size() * 2);
   hip_check(hipMemcpy(b.p, codes.data(), codes.size() * 2, hipMemcpyHostToDevice), "HLL codes H2D");
   buf = std::move(b);
   return buf.as<uint16_t>();
+}
+
+// DISTINCTCOUNT: the i32 hash code per dictId, kept beside the HLL codes and built the same way.
+const int32_t* distinct_hash_table(pgx_ctx* ctx, const StagedColumn& c) {
+  std::lock_guard<std::mutex> g(ctx->dict_mu);
+  DevBuf& buf = c.shared ? c.shared->dist_hash : c.dist_hash;
+  if (buf.p) return buf.as<int32_t>();
+  std::vector<int32_t> codes(size_t(std::max(c.card, 1)), 0);
+  for (int i = 0; i < c.card; ++i) codes[size_t(i)] = dict_hash_code(c, i);
+  DevBuf b(ctx, codes.size() * 4);
+  hip_check(hipMemcpy(b.p, codes.data(), codes.size() * 4, hipMemcpyHostToDevice), "DISTINCTCOUNT hash codes H2D");
+  buf = std::move(b);
+  return buf.as<int32_t>();
 }
 
 // workgroups per item: at least 4 steps of 256 mask words each, and no more over all items than stay resident
@@ -110,8 +79,9 @@ static int hll_wgs(const pgx_ctx* ctx, int max_words, size_t nitems) {
 // A query with DISTINCTCOUNTHLL / DISTINCTCOUNTHLLMV functions: the rest of it (its filter, its standard functions or
 // COUNT(*) alone, its GROUP BY) runs through the query kernels, which also write every scanned row's selection bit;
 // pgx_hll_offer[_group] then offers every selected row's code, pgx_hll_offer_mv[_group] the code of every value of
-// every selected doc of a multi-value column (DistinctCountHLLMVAggregationFunction.java).  Planned afresh every time
-// (no plan cache).
+// every selected doc of a multi-value column (DistinctCountHLLMVAggregationFunction.java).  DISTINCTCOUNT and
+// DISTINCTCOUNTMV functions (codes 12, 13) ride the same scan: pgx_distinct.cpp marks their presence bits on the same
+// stream and collects the result's sets afterwards.  Planned afresh every time (no plan cache).
 void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
              const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom) {
   const uint32_t xflags = opts ? opts->flags : 0;
@@ -127,24 +97,28 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   qs.flags |= PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
   qs.agg_fn.clear();
   qs.agg_col.clear();
-  std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1);
+  std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1), dist_pos(size_t(na), -1);
   std::vector<std::string> hcols;  // a column is single-value or multi-value, so the name identifies the block
   std::vector<char> hmv;           // per HLL column: multi-value (DISTINCTCOUNTHLLMV)
+  DistinctRun D;                   // DISTINCTCOUNT / DISTINCTCOUNTMV: their columns, bitmaps and items (pgx_distinct.cpp)
   for (int a = 0; a < na; ++a) {
     const int f = q.agg_fn[size_t(a)];
-    if (f == PGX_DISTINCTCOUNTHLL || f == PGX_DISTINCTCOUNTHLLMV) {
+    if (f >= PGX_DISTINCTCOUNTHLL && f <= PGX_DISTINCTCOUNTMV) {
       const std::string& c = q.agg_col[size_t(a)];
-      const bool mv = f == PGX_DISTINCTCOUNTHLLMV;
+      const bool mv = f == PGX_DISTINCTCOUNTHLLMV || f == PGX_DISTINCTCOUNTMV;
+      const bool exact = f == PGX_DISTINCTCOUNT || f == PGX_DISTINCTCOUNTMV;
       for (int s = 0; s < n; ++s) {
         const bool is_mv = segs[s]->col(c).is_mv;
-        if (!mv && is_mv) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on multi-value column " + c);
+        if (!mv && is_mv)
+          fail(PGX_ERR_UNSUPPORTED, std::string(exact ? "DISTINCTCOUNT" : "DISTINCTCOUNTHLL") + " on multi-value column " + c);
         if (mv && !is_mv) fail(PGX_ERR_UNSUPPORTED, "multi-value function on single-value column " + c);
       }
-      auto it = std::find(hcols.begin(), hcols.end(), c);
-      hll_pos[size_t(a)] = int(it - hcols.begin());
-      if (it == hcols.end()) {
-        hcols.push_back(c);
-        hmv.push_back(mv);
+      std::vector<std::string>& cols = exact ? D.cols : hcols;
+      auto it = std::find(cols.begin(), cols.end(), c);
+      (exact ? dist_pos : hll_pos)[size_t(a)] = int(it - cols.begin());
+      if (it == cols.end()) {
+        cols.push_back(c);
+        (exact ? D.mv : hmv).push_back(mv);
       }
     } else {
       if (f < PGX_COUNT || f > PGX_AVGMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
@@ -172,6 +146,8 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   const bool dense = K.group_mode == G_DENSE_LDS || K.group_mode == G_DENSE_GLOBAL;
   if (ng > 0 && (!dense || P.use_part || P.dense_slots > uint64_t(PGX_HLL_MAX_GROUP_SLOTS)))
     fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: dense key spaces of up to PGX_HLL_MAX_GROUP_SLOTS only");
+  const uint64_t slots = ng > 0 ? P.dense_slots : 1;
+  distinct_plan(ctx, segs, n, slots, D);  // (refuses tables over PGX_DISTINCT_MAX_TABLE_BYTES before anything runs)
   P.sel_off.assign(size_t(n), 0);
   int64_t words = 0;
   int max_words = 0;
@@ -195,9 +171,8 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   launch_scan(P, st);
 
   // 2. the offers, on the same stream: one item per (HLL column, segment)
-  const uint64_t slots = ng > 0 ? P.dense_slots : 1;
-  DevBuf regs(ctx, nh * slots * kHllRegs * 4);
-  hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
+  DevBuf regs(ctx, std::max<size_t>(1, nh * slots * kHllRegs * 4));
+  if (nh) hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
   std::vector<HllGroupItem> gitems;
   std::vector<HllItem> items;
   std::vector<HllMvGroupItem> mgitems;  // DISTINCTCOUNTHLLMV: the same with the docs' value ranges
@@ -259,7 +234,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   const void* mhost = ng == 0 ? static_cast<const void*>(mitems.data()) : static_cast<const void*>(mgitems.data());
   DevBuf mdev(ctx, std::max<size_t>(1, nmv) * msize);
   if (nmv) hip_check(hipMemcpyAsync(mdev.p, mhost, nmv * msize, hipMemcpyHostToDevice, st), "HLL MV items H2D");
-  const int G = hll_wgs(ctx, max_words, nitems + nmv);
+  const int G = hll_wgs(ctx, max_words, nitems + nmv + D.cols.size() * size_t(n));
   // the single-value and the multi-value items: one launch each, on the same stream, into their own register blocks
   if (scanned && nmv) {
     if (ng == 0) {
@@ -283,12 +258,18 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
                  "HLL group offers");
     }
   }
+  // the DISTINCTCOUNT[MV] marks, on the same stream
+  if (!D.cols.empty())
+    distinct_mark(ctx, q, P, segs, n, slots, rdev.as<int32_t>(), roff, G, scanned, st, D);
   pgx_result Rs;
   finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
 
   // 3. assemble in the request's order; numEntriesScannedPostFilter counts each HLL column among the projected ones
-  int extra = 0;
-  for (const auto& c : hcols)
+  int extra = 0;  // (a column both an HLL and a DISTINCTCOUNT function name counts once)
+  std::vector<std::string> special = hcols;
+  for (const auto& c : D.cols)
+    if (std::find(hcols.begin(), hcols.end(), c) == hcols.end()) special.push_back(c);
+  for (const auto& c : special)
     if (std::find(qs.agg_col.begin(), qs.agg_col.end(), c) == qs.agg_col.end() &&
         std::find(q.group_cols.begin(), q.group_cols.end(), c) == q.group_cols.end())
       ++extra;
@@ -300,13 +281,15 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   R->group_by = ng > 0;
   R->mode = Rs.mode;
   R->hll_pos = hll_pos;
+  R->dist_pos = dist_pos;
   const int64_t groups = ng > 0 ? Rs.num_groups : 1;
   R->hll_groups = groups;
   R->hll_regs.assign(nh * size_t(groups) * kHllRegs, 0);
   if (ng == 0) {
     std::vector<uint32_t> h32(nh * kHllRegs);
-    hip_check(hipMemcpy(h32.data(), regs.p, h32.size() * 4, hipMemcpyDeviceToHost), "HLL registers D2H");
+    if (nh) hip_check(hipMemcpy(h32.data(), regs.p, h32.size() * 4, hipMemcpyDeviceToHost), "HLL registers D2H");
     for (size_t i = 0; i < h32.size(); ++i) R->hll_regs[i] = uint8_t(h32[i]);
+    distinct_collect(ctx, D, std::vector<int64_t>(1, 0), slots, st, R);
     R->agg_value.assign(size_t(na), 0.0);
     R->agg_count.assign(size_t(na), 0);
     for (int a = 0; a < na; ++a)
@@ -331,7 +314,10 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
       R->g_count[size_t(a)].assign(size_t(groups), 0);
     }
   }
-  if (groups == 0) return;
+  if (groups == 0) {
+    distinct_collect(ctx, D, std::vector<int64_t>(), slots, st, R);  // (no groups: the accessors' shapes)
+    return;
+  }
   // registers of the groups the result holds: their slots from the keys (global id x gmul), narrowed on the device
   std::vector<int64_t> gslot(size_t(groups), 0);
   for (int g = 0; g < ng; ++g) {
@@ -346,6 +332,8 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   }
   for (int64_t i = 0; i < groups; ++i)
     if (gslot[size_t(i)] < 0 || uint64_t(gslot[size_t(i)]) >= slots) fail(PGX_ERR_INTERNAL, "group slot out of range");
+  distinct_collect(ctx, D, gslot, slots, st, R);
+  if (nh == 0) return;
   DevBuf sdev(ctx, size_t(groups) * 8), odev(ctx, size_t(groups) * kHllRegs);
   hip_check(hipMemcpyAsync(sdev.p, gslot.data(), size_t(groups) * 8, hipMemcpyHostToDevice, st), "HLL slots H2D");
   for (size_t k = 0; k < nh; ++k) {
@@ -367,25 +355,16 @@ extern "C" {
 pgx_status pgx_hll_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
                          uint16_t* codes) {
   return guarded([&] {
-    if (n < 0 || (n > 0 && (!values || !codes))) fail(PGX_ERR_INVALID_ARG, "bad argument");
-    if (data_type < PGX_INT || data_type > PGX_STRING) fail(PGX_ERR_INVALID_ARG, "data type");
-    if (data_type == PGX_STRING && !string_offsets) fail(PGX_ERR_INVALID_ARG, "STRING values need offsets");
-    for (int64_t i = 0; i < n; ++i) {
-      int32_t h;
-      switch (data_type) {
-        case PGX_INT: h = static_cast<const int32_t*>(values)[i]; break;
-        case PGX_LONG: h = hash_long(static_cast<const int64_t*>(values)[i]); break;
-        case PGX_FLOAT: h = hash_float(static_cast<const float*>(values)[i]); break;
-        case PGX_DOUBLE: h = hash_double(static_cast<const double*>(values)[i]); break;
-        default: {
-          const int32_t a = string_offsets[i], b = string_offsets[i + 1];
-          if (a < 0 || b < a) fail(PGX_ERR_INVALID_ARG, "string offsets not ascending");
-          h = hash_utf8(static_cast<const uint8_t*>(values) + a, size_t(b - a));
-          break;
-        }
-      }
-      codes[i] = hll_code(h);
-    }
+    if (const char* err = hash_values(data_type, values, string_offsets, n, codes, hll_code))
+      fail(PGX_ERR_INVALID_ARG, err);
+  });
+}
+
+pgx_status pgx_java_hash_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
+                               int32_t* hash_codes) {
+  return guarded([&] {
+    if (const char* err = java_hash_codes(data_type, values, string_offsets, n, hash_codes))
+      fail(PGX_ERR_INVALID_ARG, err);
   });
 }
 
@@ -397,7 +376,7 @@ pgx_status pgx_result_hll(const pgx_result* r, int32_t agg_index, int64_t first_
     if (r->select) fail(PGX_ERR_INVALID_ARG, "selection result");
     if (agg_index < 0 || agg_index >= r->num_aggs || size_t(agg_index) >= r->hll_pos.size() ||
         r->hll_pos[size_t(agg_index)] < 0)
-      fail(PGX_ERR_INVALID_ARG, "not a DISTINCTCOUNTHLL function index");
+      fail(PGX_ERR_INVALID_ARG, "not a DISTINCTCOUNTHLL function index");  // (a DISTINCTCOUNT index among them)
     if (first_group < 0 || num_groups < 0 || first_group > r->hll_groups || num_groups > r->hll_groups - first_group)
       fail(PGX_ERR_INVALID_ARG, "group range outside the result");
     if (num_groups == 0) return;

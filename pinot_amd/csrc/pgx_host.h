@@ -136,6 +136,25 @@ extern "C" hipError_t pgx_launch_hll_offer_mv_group(const pgx::HllMvGroupItem* i
                                                     hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t* slot, int64_t ngroups, int64_t slots,
                                             uint32_t* out, hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark(const pgx::DistinctItem* items, const pgx::DistinctItem* check,
+                                               int nitems, int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark_group(const pgx::DistinctGroupItem* items,
+                                                     const pgx::DistinctGroupItem* check, int nitems, int ngcols,
+                                                     const uint64_t* gmul, int64_t slots, int wgs_per_item,
+                                                     hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark_mv(const pgx::DistinctMvItem* items, const pgx::DistinctMvItem* check,
+                                                  int nitems, int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark_mv_group(const pgx::DistinctMvGroupItem* items,
+                                                        const pgx::DistinctMvGroupItem* check, int nitems, int ngcols,
+                                                        const uint64_t* gmul, int64_t slots, int wgs_per_item,
+                                                        hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_count(const uint32_t* table, int32_t card, const int64_t* rows,
+                                                int64_t nrows, int64_t slots, uint32_t* counts, int wgs,
+                                                hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_emit(const uint32_t* table, int32_t card, const int64_t* rows,
+                                               const int64_t* off, int64_t nrows, int64_t slots, const int32_t* hash,
+                                               int32_t* out, int64_t capacity, int wgs_per_row, int wgs,
+                                               hipStream_t stream);
 struct pgx_ctx;
 extern "C" void ctx_unref(pgx_ctx* ctx);
 
@@ -525,6 +544,7 @@ struct SharedDict {
   DevBuf pk_img;
   int pk_state = 0, pk_sh = 0, pk_words = 0;
   DevBuf hll_codes;  // DISTINCTCOUNTHLL: u16 register << 8 | rank per dictId, built on first use (pgx_hll.cpp; dict_mu)
+  DevBuf dist_hash;  // DISTINCTCOUNT: the i32 hash code per dictId, likewise
 };
 constexpr int kNarrowImg4Words = (160 * 1024 - 16 * 192 * 20 - 1024) / 4;  // pgx_narrow.hip kNAImg4Words
 
@@ -567,6 +587,7 @@ struct StagedColumn {
   DevBuf mv_start;
   int max_mv = 0;
   mutable DevBuf hll_codes;  // STRING columns: the DISTINCTCOUNTHLL code table (numeric: shared->hll_codes)
+  mutable DevBuf dist_hash;  // STRING columns: the DISTINCTCOUNT hash codes (numeric: shared->dist_hash)
 };
 
 inline std::atomic<uint64_t> g_segment_uid{1};
@@ -764,7 +785,15 @@ struct pgx_result {
   std::vector<int> hll_pos;
   int64_t hll_groups = 0;
   std::vector<uint8_t> hll_regs;
-  bool is_hll(int fn) const { return size_t(fn) < hll_pos.size() && hll_pos[size_t(fn)] >= 0; }
+  // DISTINCTCOUNT[MV] (run_hll, pgx_distinct.cpp): per function its column (-1: another function); per column and
+  // group where its hash codes start in dist_codes (groups + 1 entries) and the codes, ascending and unique per group
+  std::vector<int> dist_pos;
+  int64_t dist_groups = 0;
+  std::vector<std::vector<int64_t>> dist_start;
+  std::vector<std::vector<int32_t>> dist_codes;
+  bool is_distinct(int fn) const { return size_t(fn) < dist_pos.size() && dist_pos[size_t(fn)] >= 0; }
+  // a function without a numeric intermediate: pgx_result_agg, _group_values and _trim refuse its index
+  bool is_hll(int fn) const { return (size_t(fn) < hll_pos.size() && hll_pos[size_t(fn)] >= 0) || is_distinct(fn); }
   std::unique_ptr<AsyncState> async;  // declared last: destroyed (joined) before the fields its thread writes
   void ready() const;                 // waits for an async execution; throws its error
   void materialize();
@@ -1138,11 +1167,42 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
 inline bool is_standard_mv_fn(int fn) { return fn >= PGX_COUNTMV && fn <= PGX_AVGMV; }
 // A segment was staged (sign +1) or is being released (-1): its columns in ctx->col_kinds.
 void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign);
+// (DISTINCTCOUNT and DISTINCTCOUNTMV among them: all four run through run_hll and share its limits)
 inline bool query_has_hll(const pgx_query& q) {
   for (int fn : q.agg_fn)
-    if (fn == PGX_DISTINCTCOUNTHLL || fn == PGX_DISTINCTCOUNTHLLMV) return true;
+    if (fn >= PGX_DISTINCTCOUNTHLL && fn <= PGX_DISTINCTCOUNTMV) return true;
   return false;
 }
+
+// ---- pgx_distinct.cpp: DISTINCTCOUNT / DISTINCTCOUNTMV inside run_hll ----------------------------------------------
+// One presence bitmap per (column, distinct dictionary): slots rows of `words` u32.  Segments whose dictionaries are
+// the same (one SharedDict, or equal staged STRING dictionaries) mark one bitmap.
+struct DistinctBitmap {
+  const StagedColumn* col = nullptr;  // a column that holds the dictionary
+  uint32_t words = 0;
+  DevBuf table;
+  const int32_t* hash = nullptr;      // distinct_hash_table(col)
+};
+struct DistinctRun {
+  std::vector<std::string> cols;  // the query's DISTINCTCOUNT[MV] columns; mv: the multi-value form
+  std::vector<char> mv;
+  std::vector<std::vector<DistinctBitmap>> maps;  // per column
+  std::vector<std::vector<int>> map_of;           // per column and segment: its bitmap
+  // the mark kernels' items and their device copies, alive until the stream was waited for
+  std::vector<pgx::DistinctItem> items;
+  std::vector<pgx::DistinctGroupItem> gitems;
+  std::vector<pgx::DistinctMvItem> mitems;
+  std::vector<pgx::DistinctMvGroupItem> mgitems;
+  DevBuf idev, mdev;
+};
+const int32_t* distinct_hash_table(pgx_ctx* ctx, const StagedColumn& c);  // pgx_hll.cpp, beside the HLL code tables
+void distinct_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots, DistinctRun& D);
+void distinct_mark(pgx_ctx* ctx, const pgx_query& q, const ExecPlan& P, pgx_segment* const* segs, int n, uint64_t slots,
+                   const int32_t* remaps, const std::map<const std::vector<int32_t>*, size_t>& remap_off, int wgs,
+                   bool scanned, hipStream_t st, DistinctRun& D);
+// rows: the table row (slot) of every group of the result, in its order
+void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& rows, uint64_t slots, hipStream_t st,
+                      pgx_result* R);
 
 void parse_star_tree(pgx_segment& seg);
 void stage_column(pgx_ctx* ctx, pgx_segment* seg, const pgx_column_desc& d, bool device_mem, StagedColumn& c);

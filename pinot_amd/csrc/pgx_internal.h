@@ -190,6 +190,39 @@ struct HllGroupKey {           // passed by value: slot = sum over the group col
   int32_t pad;
 };
 
+// DISTINCTCOUNT / DISTINCTCOUNTMV (pgx_distinct.hip; DistinctCountAggregationFunction): one item per (segment,
+// function), laid out like the HLL items.  The state is one presence bit per dictId, (card + 31) / 32 u32 words per
+// dictionary (under GROUP BY one such row per slot); bits are only ever ORed in, so items that share `out` combine.
+constexpr int kDistinctLdsWords = 8192;  // bitmaps of up to 32 KiB (card <= 262,144) are marked in LDS
+struct DistinctItem {
+  const uint32_t* sel;         // selected docs: bit (d & 31) of word d >> 5 (written by the query kernel)
+  const uint32_t* fwd;         // packed big-endian fixed-bit forward index, padded to whole tiles
+  uint32_t* out;               // (card + 31) / 32 words; the group kernels: slots rows of that many words
+  int32_t bits;
+  int32_t num_docs;
+  int32_t card;                // dictIds at or past it mark nothing; bits at or past it are never set
+  int32_t pad;
+};
+struct DistinctGroupItem {
+  DistinctItem d;
+  HllGCol g[kMaxGroupCols];
+};
+struct DistinctMvItem {        // d.fwd is the value stream, doc i owns the value rows start[i] .. start[i + 1] - 1
+  DistinctItem d;
+  const int32_t* start;        // num_docs + 1 ascending entries; entries past index num_docs are never read
+  int32_t total;               // value rows of the stream: rows at or past it are never read, whatever start[] holds
+  int32_t pad;
+};
+struct DistinctMvGroupItem {
+  DistinctGroupItem g;
+  const int32_t* start;
+  int32_t total;
+  int32_t pad;
+};
+static_assert(sizeof(DistinctItem) == 40 && sizeof(DistinctGroupItem) == 40 + kMaxGroupCols * 24 &&
+                  sizeof(DistinctMvItem) == 56 && sizeof(DistinctMvGroupItem) == sizeof(DistinctGroupItem) + 16,
+              "tests/distinct_ref.py mirrors these");
+
 // Statistics automaton over one segment's leaf masks (pgx_kernels.hip pgx_fsm_chunks / pgx_fsm_compose).
 struct FsmSeg {
   const uint32_t* lmask;       // leaf l, row r: bit (r & 31) of word [l * words + (r >> 5)]

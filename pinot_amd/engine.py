@@ -29,8 +29,10 @@ from .segment import Column, SegmentData
 _DT = {"INT": N.PGX_INT, "LONG": N.PGX_LONG, "FLOAT": N.PGX_FLOAT, "DOUBLE": N.PGX_DOUBLE, "STRING": N.PGX_STRING}
 _FN = {"count": N.PGX_COUNT, "sum": N.PGX_SUM, "min": N.PGX_MIN, "max": N.PGX_MAX, "avg": N.PGX_AVG,
        "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV,
-       "distinctcounthll": N.PGX_DISTINCTCOUNTHLL, "distinctcounthllmv": N.PGX_DISTINCTCOUNTHLLMV}
+       "distinctcounthll": N.PGX_DISTINCTCOUNTHLL, "distinctcounthllmv": N.PGX_DISTINCTCOUNTHLLMV,
+       "distinctcount": N.PGX_DISTINCTCOUNT, "distinctcountmv": N.PGX_DISTINCTCOUNTMV}
 _HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # their intermediates are register sets (pgx_result_hll)
+_DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... sets of Java hash codes (pgx_result_distinct)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -739,6 +741,19 @@ def result_hll(r, fn_index: int, first_group: int = 0, num_groups: int = 1) -> n
     return regs[:num_groups]
 
 
+def result_distinct(r, fn_index: int, first_group: int = 0, num_groups: int = 1) -> List[set]:
+    """pgx_result_distinct_counts and pgx_result_distinct: the hash-code set of a DISTINCTCOUNT[MV] function per group
+    (one "group" for an aggregation-only result)."""
+    counts = np.zeros(max(num_groups, 1), dtype=np.int64)
+    N.check(N.lib().pgx_result_distinct_counts(r, fn_index, first_group, num_groups, counts.ctypes.data))
+    ends = np.cumsum(counts[:num_groups])
+    total = int(ends[-1]) if num_groups else 0
+    codes = np.zeros(max(total, 1), dtype=np.int32)
+    N.check(N.lib().pgx_result_distinct(r, fn_index, first_group, num_groups, codes.ctypes.data, total))
+    flat = codes[:total].tolist()
+    return [set(flat[int(e - c):int(e)]) for c, e in zip(counts[:num_groups], ends)]
+
+
 def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = False) -> IntermediateResultsBlock:
     L = N.lib()
     st = (C.c_int64 * 4)()
@@ -749,6 +764,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
         for i, fn in enumerate(q.fns):
             if fn in _HLL_FNS:  # the intermediate is the register set (hll.py)
                 out.append(result_hll(r, i)[0])
+                continue
+            if fn in _DISTINCT_FNS:  # the set of hash codes
+                out.append(result_distinct(r, i)[0])
                 continue
             v, c = C.c_double(), C.c_int64()
             N.check(L.pgx_result_agg(r, i, C.byref(v), C.byref(c)))
@@ -779,6 +797,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
         if fn in _HLL_FNS:
             vals.append(list(result_hll(r, i, 0, n)))
             continue
+        if fn in _DISTINCT_FNS:
+            vals.append(result_distinct(r, i, 0, n))
+            continue
         v = np.zeros(max(n, 1), dtype=np.float64)
         c = np.zeros(max(n, 1), dtype=np.int64)
         N.check(L.pgx_result_group_values(r, i, v.ctypes.data, c.ctypes.data))
@@ -794,7 +815,7 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if trim:
         trimmed = []
         for i in range(len(q.fns)):
-            if q.fns[i] in _HLL_FNS:  # no order to trim by: every group (pgx_result_trim refuses the index)
+            if q.fns[i] in _HLL_FNS or q.fns[i] in _DISTINCT_FNS:  # no order to trim by: every group (pgx_result_trim refuses the index)
                 trimmed.append({keys[j]: per_group[j][i] for j in range(n)})
                 continue
             cap = C.c_int64(n)

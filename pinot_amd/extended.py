@@ -3,7 +3,10 @@ decomposed on the host into GPU sub-queries the fused scan kernels already run:
 
 * MINMAXRANGE(c) -> MIN(c) and MAX(c) in the base query; intermediate (min, max)
   (core/operator/aggregation/function/MinMaxRangeAggregationFunction.java aggregate: a Pair of block extremes);
-* DISTINCTCOUNT(c) -> ``GROUP BY c`` with COUNT(*) under the same filter; intermediate the set of the values' Java
+* DISTINCTCOUNT(c) -> a function of the base query itself (PGX_DISTINCTCOUNT, DISTINCTCOUNTMV(c) PGX_DISTINCTCOUNTMV:
+  presence bits per dictId marked on the device, the set read with pgx_result_distinct; ``native_distinct``).  Where
+  the library refuses the shape, or with PGX_DISTINCT_NATIVE=0, ``GROUP BY c`` with COUNT(*) under the same filter;
+  intermediate the set of the values' Java
   hashCode()s: the executor hands DISTINCTCOUNT / DISTINCTCOUNTHLL ``getSVHashCodeArray()``
   (operator/aggregation/DefaultAggregationExecutor.java:135-139, common/DataFetcher.java:242-248:
   ``dictionary.get(dictId).hashCode()``), and the function adds ``(int) hash`` (operator/aggregation/function/
@@ -38,6 +41,7 @@ from .pql import EXT_FUNCTIONS, EXT_MV_FUNCTIONS
 
 _HIST_FNS = ("distinctcount", "distinctcounthll", "fasthll")
 _NATIVE_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # functions of the base query when `native_hll`
+_NATIVE_DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... when `native_distinct`
 
 
 def base_fn(fn: str) -> str:
@@ -133,6 +137,11 @@ def _projection_count(request: dict) -> int:
     return len(cols)
 
 
+def _star_tree_request(request: dict, segments) -> bool:
+    use_st = str((request.get("debug_options") or {}).get("useStarTree", "true")).lower() != "false"
+    return use_st and any(getattr(s.data, "star_tree", None) is not None for s in segments)
+
+
 def native_hll(request: dict, segments) -> bool:
     """Whether the request's DISTINCTCOUNTHLL and DISTINCTCOUNTHLLMV functions run inside the base query
     (PGX_DISTINCTCOUNTHLL / PGX_DISTINCTCOUNTHLLMV: registers computed on the device, pgx_hll.hip) instead of through the ``GROUP BY c`` histogram.  PGX_HLL_NATIVE=0
@@ -142,19 +151,29 @@ def native_hll(request: dict, segments) -> bool:
         return False
     if not any(a["fn"] in _NATIVE_HLL_FNS for a in request["aggregations"]):
         return False
-    use_st = str((request.get("debug_options") or {}).get("useStarTree", "true")).lower() != "false"
-    return not (use_st and any(getattr(s.data, "star_tree", None) is not None for s in segments))
+    return not _star_tree_request(request, segments)
 
 
-def _base_request(request: dict, native: bool = False):
-    """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE; with `native` the
-    DISTINCTCOUNTHLL and DISTINCTCOUNTHLLMV functions as well) and, per original function, its base slot: an index, a (min, max) index pair,
-    or None (histogram functions)."""
+def native_distinct(request: dict, segments) -> bool:
+    """Whether the request's DISTINCTCOUNT and DISTINCTCOUNTMV functions run inside the base query (PGX_DISTINCTCOUNT /
+    PGX_DISTINCTCOUNTMV, pgx_distinct.hip), by ``native_hll``'s rules: PGX_DISTINCT_NATIVE=0 forces the histogram, and a
+    request whose base query a star tree could answer keeps the decomposition."""
+    if os.environ.get("PGX_DISTINCT_NATIVE", "1") == "0":
+        return False
+    if not any(a["fn"] in _NATIVE_DISTINCT_FNS for a in request["aggregations"]):
+        return False
+    return not _star_tree_request(request, segments)
+
+
+def _base_request(request: dict, native: Sequence[str] = ()):
+    """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE, and the functions named
+    in `native`: DISTINCTCOUNTHLL[MV], DISTINCTCOUNT[MV]) and, per original function, its base slot: an index, a
+    (min, max) index pair, or None (histogram functions)."""
     base = [{"fn": "count", "column": "*"}]
     slot = []
     for a in request["aggregations"]:
         fn = a["fn"]
-        if native and fn in _NATIVE_HLL_FNS:
+        if fn in native:
             base.append(dict(a))
             slot.append(len(base) - 1)
         elif fn == "minmaxrange":
@@ -172,12 +191,12 @@ def _dtype(segments, col: str) -> str:
     return segments[0].column(col).meta.data_type if segments else "INT"
 
 
-def _hist_columns(request: dict, segments, native: bool = False) -> List[str]:
+def _hist_columns(request: dict, segments, native: Sequence[str] = ()) -> List[str]:
     cols = []
     for a in request["aggregations"]:
         mv = a["fn"] in EXT_MV_FUNCTIONS
         fn = base_fn(a["fn"])
-        if native and a["fn"] in _NATIVE_HLL_FNS:  # in the base query: no histogram on its account
+        if a["fn"] in native:  # in the base query: no histogram on its account
             continue
         if fn not in _HIST_FNS and fn != "minmaxrange" and not fn.startswith("percentile"):
             continue
@@ -214,7 +233,7 @@ def _numeric(hist) -> List:
     return [(float(v), c) for v, c in hist]
 
 
-def _run_group_by(ctx, request, segments, combine, native: bool = False) -> E.IntermediateResultsBlock:
+def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -> E.IntermediateResultsBlock:
     """Group-by: the base request keeps the GROUP BY columns; each histogram column c runs ``GROUP BY <columns>, c``
     with COUNT(*), and its groups are folded back per leading key (the group string minus its last field).  The
     combine trim keeps the base request's trimmed maps for the standard functions; functions whose intermediates the
@@ -259,7 +278,7 @@ def _run_group_by(ctx, request, segments, combine, native: bool = False) -> E.In
             return (float(h[0][0]), float(h[-1][0])) if h else (math.inf, -math.inf)
         if fn == "minmaxrange":
             return (float(bvals[s[0]]), float(bvals[s[1]]))
-        if fn == "distinctcount":
+        if fn == "distinctcount" and s is None:
             return _hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, []))
         if fn == "distinctcounthll" and s is None:
             return HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, [])))
@@ -292,13 +311,22 @@ def _run_group_by(ctx, request, segments, combine, native: bool = False) -> E.In
 
 def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
         combine: bool = True) -> E.IntermediateResultsBlock:
-    if native_hll(request, segments):
+    """Native where the library takes the shape: first with the HLL and the DISTINCTCOUNT functions in the base query,
+    then with the HLL functions alone (an HLL function keeps its native path when a DISTINCTCOUNT beside it is refused),
+    then the full decomposition."""
+    hll, dist = native_hll(request, segments), native_distinct(request, segments)
+    routes = []
+    if dist:
+        routes.append(_NATIVE_DISTINCT_FNS + (_NATIVE_HLL_FNS if hll else ()))
+    if hll:
+        routes.append(_NATIVE_HLL_FNS)
+    for native in routes:
         try:
-            return _run(ctx, request, segments, combine, True)
-        except N.PgxError as e:  # a shape the native path refuses runs as the decomposition
+            return _run(ctx, request, segments, combine, native)
+        except N.PgxError as e:  # a shape the native path refuses runs as the next route
             if e.status != N.PGX_ERR_UNSUPPORTED:
                 raise
-    return _run(ctx, request, segments, combine, False)
+    return _run(ctx, request, segments, combine, ())
 
 
 def _run(ctx, request, segments, combine, native) -> E.IntermediateResultsBlock:
@@ -334,7 +362,7 @@ def _run(ctx, request, segments, combine, native) -> E.IntermediateResultsBlock:
             out.append((float(h[0][0]), float(h[-1][0])) if h else (math.inf, -math.inf))
         elif fn == "minmaxrange":
             out.append((float(base_res[s[0]]), float(base_res[s[1]])))
-        elif fn == "distinctcount":
+        elif fn == "distinctcount" and s is None:
             out.append(_hash_set(_dtype(segments, a["column"]), hists[a["column"]]))
         elif fn == "distinctcounthll" and s is None:
             out.append(HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]])))

@@ -21,7 +21,10 @@ PGX_INT, PGX_LONG, PGX_FLOAT, PGX_DOUBLE, PGX_STRING = range(5)
 PGX_COUNT, PGX_SUM, PGX_MIN, PGX_MAX, PGX_AVG, PGX_COUNTMV, PGX_SUMMV, PGX_MINMV, PGX_MAXMV, PGX_AVGMV = range(10)
 PGX_DISTINCTCOUNTHLL = 10
 PGX_DISTINCTCOUNTHLLMV = 11
+PGX_DISTINCTCOUNT = 12
+PGX_DISTINCTCOUNTMV = 13
 PGX_HLL_MAX_GROUP_SLOTS = 65536
+PGX_DISTINCT_MAX_TABLE_BYTES = 256 << 20
 PGX_PRED = {"EQ": 0, "NEQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 PGX_F_LEAF, PGX_F_AND, PGX_F_OR = 0, 1, 2
 PGX_MEM_HOST, PGX_MEM_DEVICE = 0, 1
@@ -180,6 +183,9 @@ EXPORTS = {
     "pgx_mutable_release": (C.c_int, [C.c_void_p]),
     "pgx_result_hll": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "pgx_hll_codes": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pgx_result_distinct_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "pgx_result_distinct": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "pgx_java_hash_codes": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "pgx_timing_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]),
 }
 
