@@ -2,7 +2,8 @@
 // the scan's stream, and the result: set sizes and hash codes per group, read with pgx_result_distinct_counts and
 // pgx_result_distinct.  DistinctCountAggregationFunction (operator/aggregation/function/
 // DistinctCountAggregationFunction.java): the intermediate is the set of (int) hashCode over the selected docs' values,
-// combine is set union, reduce its size.  The kernels are in pgx_distinct.hip.
+// combine is set union, reduce its size.  The kernels are in pgx_distinct.hip; the items are built and launched by the
+// SelItems of pgx_host.h, as the HLL offers' are.
 #include "pgx_hash.h"
 #include "pgx_host.h"
 
@@ -47,78 +48,23 @@ void distinct_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots
 }
 
 // One item per (column, segment), one launch for the single-value and one for the multi-value columns.
-void distinct_mark(pgx_ctx* ctx, const pgx_query& q, const ExecPlan& P, pgx_segment* const* segs, int n, uint64_t slots,
-                   const int32_t* remaps, const std::map<const std::vector<int32_t>*, size_t>& remap_off, int wgs,
-                   bool scanned, hipStream_t st, DistinctRun& D) {
-  const int ng = int(q.group_cols.size());
+void distinct_mark(pgx_ctx* ctx, const SelScan& S, DistinctRun& D) {
   for (auto& maps : D.maps)
     for (auto& m : maps)
-      hip_check(hipMemsetAsync(m.table.p, 0, size_t(slots) * m.words * 4, st), "DISTINCTCOUNT bitmaps");
+      hip_check(hipMemsetAsync(m.table.p, 0, size_t(S.slots) * m.words * 4, S.st), "DISTINCTCOUNT bitmaps");
   for (size_t k = 0; k < D.cols.size(); ++k)
-    for (int s = 0; s < n; ++s) {
-      const StagedColumn& col = segs[s]->col(D.cols[k]);
+    for (int s = 0; s < S.n; ++s) {
+      const StagedColumn& col = S.segs[s]->col(D.cols[k]);
       pgx::DistinctItem d{};
-      d.sel = P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)];
-      d.fwd = col.fwd;
       d.out = D.maps[k][size_t(D.map_of[k][size_t(s)])].table.as<uint32_t>();
-      d.bits = col.bits;
-      d.num_docs = P.ksegs[size_t(s)].num_docs;
       d.card = col.card;
-      if (!d.fwd) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNT on a column without a forward index: " + col.name);
-      const int32_t* start = D.mv[k] ? col.mv_start.as<const int32_t>() : nullptr;
-      if (D.mv[k] && (!start || col.total_entries < 0 || col.total_entries > INT32_MAX))
-        fail(PGX_ERR_INTERNAL, "multi-value column without value ranges: " + col.name);
-      if (ng == 0) {
-        if (D.mv[k]) D.mitems.push_back(pgx::DistinctMvItem{d, start, int32_t(col.total_entries), 0});
-        else D.items.push_back(d);
-        continue;
-      }
-      pgx::DistinctGroupItem gi{};
-      gi.d = d;
-      for (int g = 0; g < ng; ++g) {
-        const StagedColumn& gc = segs[s]->col(q.group_cols[size_t(g)]);
-        if (!gc.fwd) fail(PGX_ERR_UNSUPPORTED, "GROUP BY a column without a forward index: " + gc.name);
-        gi.g[g].fwd = gc.fwd;
-        gi.g[g].bits = gc.bits;
-        const GlobalDict& gd = P.gdicts[size_t(g)];
-        if (!gd.identity && gd.remap[size_t(s)]) gi.g[g].remap = remaps + remap_off.at(gd.remap[size_t(s)].get());
-      }
-      if (D.mv[k]) D.mgitems.push_back(pgx::DistinctMvGroupItem{gi, start, int32_t(col.total_entries), 0});
-      else D.gitems.push_back(gi);
+      D.items.add(S, s, col, D.mv[k], "DISTINCTCOUNT", d);
     }
-  const size_t nsv = ng == 0 ? D.items.size() : D.gitems.size();
-  const size_t ssize = ng == 0 ? sizeof(pgx::DistinctItem) : sizeof(pgx::DistinctGroupItem);
-  const void* shost = ng == 0 ? static_cast<const void*>(D.items.data()) : static_cast<const void*>(D.gitems.data());
-  D.idev = DevBuf(ctx, std::max<size_t>(1, nsv) * ssize);
-  if (nsv) hip_check(hipMemcpyAsync(D.idev.p, shost, nsv * ssize, hipMemcpyHostToDevice, st), "DISTINCTCOUNT items H2D");
-  const size_t nmv = ng == 0 ? D.mitems.size() : D.mgitems.size();
-  const size_t msize = ng == 0 ? sizeof(pgx::DistinctMvItem) : sizeof(pgx::DistinctMvGroupItem);
-  const void* mhost = ng == 0 ? static_cast<const void*>(D.mitems.data()) : static_cast<const void*>(D.mgitems.data());
-  D.mdev = DevBuf(ctx, std::max<size_t>(1, nmv) * msize);
-  if (nmv)
-    hip_check(hipMemcpyAsync(D.mdev.p, mhost, nmv * msize, hipMemcpyHostToDevice, st), "DISTINCTCOUNTMV items H2D");
-  if (!scanned) return;  // every segment empty: the bitmaps stay zero
-  const uint64_t* gmul = P.kq.gmul;
-  if (nsv && ng == 0) {
-    PGX_LAUNCH(st, "pgx_distinct_mark",
-               pgx_launch_distinct_mark(D.idev.as<pgx::DistinctItem>(), D.items.data(), int(nsv), wgs, st),
-               "DISTINCTCOUNT marks");
-  } else if (nsv) {
-    PGX_LAUNCH(st, "pgx_distinct_mark_group",
-               pgx_launch_distinct_mark_group(D.idev.as<pgx::DistinctGroupItem>(), D.gitems.data(), int(nsv), ng, gmul,
-                                              int64_t(slots), wgs, st),
-               "DISTINCTCOUNT group marks");
-  }
-  if (nmv && ng == 0) {
-    PGX_LAUNCH(st, "pgx_distinct_mark_mv",
-               pgx_launch_distinct_mark_mv(D.mdev.as<pgx::DistinctMvItem>(), D.mitems.data(), int(nmv), wgs, st),
-               "DISTINCTCOUNTMV marks");
-  } else if (nmv) {
-    PGX_LAUNCH(st, "pgx_distinct_mark_mv_group",
-               pgx_launch_distinct_mark_mv_group(D.mdev.as<pgx::DistinctMvGroupItem>(), D.mgitems.data(), int(nmv), ng,
-                                                 gmul, int64_t(slots), wgs, st),
-               "DISTINCTCOUNTMV group marks");
-  }
+  D.items.upload(ctx, S.st, "DISTINCTCOUNT items H2D", "DISTINCTCOUNTMV items H2D");
+  D.items.launch_sv(S, "pgx_distinct_mark", pgx_launch_distinct_mark, "DISTINCTCOUNT marks",
+                    "pgx_distinct_mark_group", pgx_launch_distinct_mark_group, "DISTINCTCOUNT group marks");
+  D.items.launch_mv(S, "pgx_distinct_mark_mv", pgx_launch_distinct_mark_mv, "DISTINCTCOUNTMV marks",
+                    "pgx_distinct_mark_mv_group", pgx_launch_distinct_mark_mv_group, "DISTINCTCOUNTMV group marks");
 }
 
 // The result's groups: per bitmap the rows' sizes (pgx_distinct_count), then exactly that many hash codes

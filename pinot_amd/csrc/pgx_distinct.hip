@@ -23,6 +23,8 @@
 //                               caller's offset for that row on; positions come from a prefix over the word popcounts.
 //                               Grid (workgroups per row, rows): a workgroup takes one stretch of the row's words and
 //                               counts the bits of the words before it itself.
+// The walk over the selection bits is shared with pgx_hll.hip and lives in pgx_hll_device.h; here are the marks it is
+// handed, the result kernels and the launchers.
 // No workgroup waits on another; all stores are plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
 
@@ -33,21 +35,8 @@ namespace pgx {
 
 constexpr uint32_t kDistinctNone = 0xFFFFFFFFu;  // no dictId: card <= INT32_MAX
 
-// mask words of an item; an item with a count, width or cardinality out of range has no rows
-__device__ __forceinline__ int dist_words(const DistinctItem& A) {
-  return A.num_docs > 0 && A.bits >= 1 && A.bits <= 32 && A.card >= 1 ? (A.num_docs + 31) >> 5 : 0;
-}
-
 __device__ __host__ __forceinline__ uint32_t dist_bitmap_words(int32_t card) {
   return (static_cast<uint32_t>(card) + 31u) >> 5;  // card >= 1
-}
-
-// mask word w of the item without the bits at and past num_docs (the spare word is never read: w < words)
-__device__ __forceinline__ uint32_t dist_mask_word(const DistinctItem& A, int64_t w) {
-  uint32_t sel = A.sel[w];
-  const int32_t left = A.num_docs - static_cast<int32_t>(w * 32);
-  if (left < 32) sel &= (1u << left) - 1u;
-  return sel;
 }
 
 // bit `id` of the bitmap bm (LDS or HBM), id < card
@@ -75,24 +64,17 @@ __device__ __forceinline__ void dist_mark_word(uint32_t* bm, const DistinctItem&
 }
 
 __device__ __forceinline__ void dist_scan(uint32_t* bm, const DistinctItem& A, int words) {
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x; w < words; w += stride) {
-    const uint32_t sel = dist_mask_word(A, w);
-    if (sel == 0u) continue;
-    if (__builtin_popcount(sel) >= kHllDenseRows) {
-      uint32_t v[32];
-      hll_decode_word(A.bits, A.fwd, w, v);
-      dist_mark_word(bm, A, sel, v);
-    } else {
-      const int32_t d0 = static_cast<int32_t>(w * 32);
-      for (uint32_t m = sel; m;) {
-        const int k = __builtin_ctz(m);
-        m &= m - 1u;
-        const uint32_t id = hll_value(A.fwd, d0 + k, A.bits);
+  sel_walk(
+      A, words,
+      [&](int64_t w, uint32_t sel) PGX_SEL_OP {
+        uint32_t v[32];
+        hll_decode_word(A.bits, A.fwd, w, v);
+        dist_mark_word(bm, A, sel, v);
+      },
+      [&](int32_t row) PGX_SEL_OP {
+        const uint32_t id = hll_value(A.fwd, row, A.bits);
         if (id < static_cast<uint32_t>(A.card)) dist_mark(bm, id);
-      }
-    }
-  }
+      });
 }
 
 // the workgroup's LDS bitmap into the item's: only words that hold a bit, and an atomic only where one is new
@@ -108,7 +90,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark(const DistinctIte
   if (item >= nitems) return;
   __shared__ uint32_t lbits[kDistinctLdsWords];
   const DistinctItem A = items[item];
-  const int words = dist_words(A);
+  const int words = sel_words(A);
   if (words == 0) return;  // (the whole workgroup)
   const uint32_t bw = dist_bitmap_words(A.card);
   if (bw <= static_cast<uint32_t>(kDistinctLdsWords)) {
@@ -123,17 +105,6 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark(const DistinctIte
 }
 
 // ---- GROUP BY: single-value group columns -> a dense slot ----------------------------------------------------------
-// the slot of one row, or kHllNoSlot or more: a remap of -1, or a key outside the planned space
-__device__ __forceinline__ uint32_t dist_row_slot(const DistinctGroupItem& G, const HllGroupKey& K, int32_t row) {
-  uint32_t s = 0u;
-  for (int g = 0; g < K.ngcols; ++g) {
-    const uint32_t id = hll_value(G.g[g].fwd, row, G.g[g].bits);
-    const uint32_t gid = G.g[g].remap ? static_cast<uint32_t>(G.g[g].remap[id]) : id;  // a negative id: >= 2^31
-    s = hll_mv_fold(s, gid, static_cast<uint32_t>(K.gmul[g]));
-  }
-  return s;
-}
-
 // Rows J0 .. J0 + 15 of a mask word whose dictIds are decoded (v): slots, bitmap words, atomics.  Half a word at a
 // time: 16 loads in flight per lane and pass.  The word's rows all lie inside the group columns' padded indexes, so the
 // id loads are unconditional; a row that marks nothing takes remap entry 0 and reads word 0 of the table.
@@ -172,43 +143,29 @@ __device__ __forceinline__ void dist_group_rows(const DistinctGroupItem& G, cons
       atomicOr(&table[static_cast<size_t>(s[j]) * bw + (v[J0 + j] >> 5)], 1u << (v[J0 + j] & 31u));
 }
 
-__device__ __forceinline__ bool dist_gcols_ok(const DistinctGroupItem& G, const HllGroupKey& K) {
-  bool ok = true;
-  for (int g = 0; g < K.ngcols; ++g) ok = ok && G.g[g].bits >= 1 && G.g[g].bits <= 32;
-  return ok;
-}
-
 __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_group(const DistinctGroupItem* __restrict__ items,
                                                                      int nitems, const HllGroupKey K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   const DistinctGroupItem& G = items[item];
   const DistinctItem A = G.d;
-  const int words = dist_gcols_ok(G, K) ? dist_words(A) : 0;
   const uint32_t slots32 = static_cast<uint32_t>(K.slots);
   const uint32_t bw = dist_bitmap_words(A.card);
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x; w < words; w += stride) {
-    uint32_t sel = dist_mask_word(A, w);
-    if (sel == 0u) continue;
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    if (__builtin_popcount(sel) >= kHllDenseRows) {
-      uint32_t v[32];
-      hll_decode_word(A.bits, A.fwd, w, v);
+  sel_walk(
+      A, sel_gcols_ok(G.g, K) ? sel_words(A) : 0,
+      [&](int64_t w, uint32_t sel) PGX_SEL_OP {
+        uint32_t v[32];
+        hll_decode_word(A.bits, A.fwd, w, v);
 #pragma unroll
-      for (int j = 0; j < 32; ++j) sel &= ~(static_cast<uint32_t>(v[j] >= static_cast<uint32_t>(A.card)) << j);
-      dist_group_rows<0>(G, K, sel, d0, v);
-      dist_group_rows<16>(G, K, sel, d0, v);
-    } else {
-      for (uint32_t m = sel; m;) {
-        const int k = __builtin_ctz(m);
-        m &= m - 1u;
-        const uint32_t id = hll_value(A.fwd, d0 + k, A.bits);
-        const uint32_t s = dist_row_slot(G, K, d0 + k);
+        for (int j = 0; j < 32; ++j) sel &= ~(static_cast<uint32_t>(v[j] >= static_cast<uint32_t>(A.card)) << j);
+        dist_group_rows<0>(G, K, sel, static_cast<int32_t>(w * 32), v);
+        dist_group_rows<16>(G, K, sel, static_cast<int32_t>(w * 32), v);
+      },
+      [&](int32_t row) PGX_SEL_OP {
+        const uint32_t id = hll_value(A.fwd, row, A.bits);
+        const uint32_t s = sel_row_slot(G.g, K, row);
         if (id < static_cast<uint32_t>(A.card) && s < slots32) dist_mark(A.out + static_cast<size_t>(s) * bw, id);
-      }
-    }
-  }
+      });
 }
 
 // ---- DISTINCTCOUNTMV: every value of every selected doc --------------------------------------------------------------
@@ -219,7 +176,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_group(const Disti
 template <int N>
 __device__ __forceinline__ void dist_mv_batch(uint32_t* bm, const DistinctItem& A, uint32_t lo, uint32_t hi) {
   uint32_t v[N];
-  const uint32_t card = static_cast<uint32_t>(A.card);  // >= 1 (dist_words)
+  const uint32_t card = static_cast<uint32_t>(A.card);  // >= 1 (sel_words)
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     const uint32_t r = lo + static_cast<uint32_t>(i);
@@ -240,118 +197,45 @@ __device__ __forceinline__ void dist_mv_batch(uint32_t* bm, const DistinctItem& 
     if (v[i] != kDistinctNone) atomicOr(&bm[v[i] >> 5], 1u << (v[i] & 31u));
 }
 
-constexpr int kDistinctMvBatch = 16;  // value rows per pass of a long range
-constexpr int kDistinctMvShort = 4;   // ... of a range's last rows (a sparse word's doc has a few values only)
-
-// value rows [lo, hi) clamped to the stream: start[] is device data nobody validated
-__device__ __forceinline__ void dist_mv_range(uint32_t* bm, const DistinctItem& A, int32_t total, int32_t lo,
-                                              int32_t hi) {
-  uint32_t a = static_cast<uint32_t>(lo < 0 ? 0 : lo);
-  const uint32_t b = static_cast<uint32_t>(hi < 0 ? 0 : hi < total ? hi : total);  // total > 0 (dist_mv_words)
-  while (a < b && b - a > static_cast<uint32_t>(kDistinctMvShort)) {
-    dist_mv_batch<kDistinctMvBatch>(bm, A, a, b);
-    a += kDistinctMvBatch;
-  }
-  if (a < b) dist_mv_batch<kDistinctMvShort>(bm, A, a, b);
-}
-
-__device__ __forceinline__ int dist_mv_words(const DistinctItem& A, const int32_t* start, int32_t total) {
-  return start && total > 0 ? dist_words(A) : 0;
-}
-
-// A maximal run of selected docs a .. a + len - 1 of a mask word owns one contiguous value range: ranges are walked,
-// not docs, and a fully selected word is one range.  One lane walks a range alone.
-__device__ __forceinline__ void dist_mv_scan(uint32_t* bm, const DistinctMvItem& M, int words) {
-  const DistinctItem& A = M.d;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x; w < words; w += stride) {
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    for (uint32_t m = dist_mask_word(A, w); m;) {  // (bits at and past num_docs are off: d0 + a + len <= num_docs)
-      const int a = __builtin_ctz(m);
-      const uint32_t rest = ~(m >> a);
-      const int len = rest ? __builtin_ctz(rest) : 32;
-      m &= ~((len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u)) << a);
-      dist_mv_range(bm, A, M.total, M.start[d0 + a], M.start[d0 + a + len]);
-    }
-  }
-}
-
+// A run of consecutive selected docs owns one contiguous range of the value stream (sel_mv_walk).
 __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_mv(const DistinctMvItem* __restrict__ items,
                                                                   int nitems) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t lbits[kDistinctLdsWords];
   const DistinctMvItem M = items[item];
-  const int words = dist_mv_words(M.d, M.start, M.total);
+  const int words = sel_mv_words(M.d, M.start, M.total);
   if (words == 0) return;  // (the whole workgroup)
   const uint32_t bw = dist_bitmap_words(M.d.card);
+  const auto scan = [&](uint32_t* bm) PGX_SEL_OP {
+    sel_mv_walk(M.d, words, M.start, M.total, [&](auto n, uint32_t lo, uint32_t hi) PGX_SEL_OP {
+      dist_mv_batch<decltype(n)::value>(bm, M.d, lo, hi);
+    });
+  };
   if (bw <= static_cast<uint32_t>(kDistinctLdsWords)) {
     for (uint32_t i = threadIdx.x; i < bw; i += kHllBlock) lbits[i] = 0u;
     __syncthreads();
-    dist_mv_scan(lbits, M, words);
+    scan(lbits);
     __syncthreads();
     dist_flush(lbits, M.d.out, bw);
   } else {
-    dist_mv_scan(M.d.out, M, words);
+    scan(M.d.out);
   }
 }
 
-// The same into the slots' rows in HBM.  A doc's slot comes from its single-value group columns; every value of the
-// doc goes to that slot's row, so ranges are walked per doc.  A word's slots are computed first, for a dense word in
-// passes of independent loads over its 32 docs (all inside the group columns' padded indexes; a doc that is not
-// selected takes remap entry 0), and parked in LDS: one column of 32 per thread, which only that thread touches.
+// The same into the slots' rows in HBM: every value of a doc into the row of the doc's slot (sel_mv_group_walk).
 __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_mv_group(const DistinctMvGroupItem* __restrict__ items,
                                                                         int nitems, const HllGroupKey K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t slot_of[32 * kHllBlock];
   const DistinctMvGroupItem& M = items[item];
-  const DistinctGroupItem& G = M.g;
-  const DistinctItem A = G.d;
-  const int32_t* __restrict__ start = M.start;
-  const int32_t total = M.total;
-  const int tid = static_cast<int>(threadIdx.x);
-  uint32_t* const mine = slot_of + tid;  // doc j of the word: mine[j * kHllBlock]
-  const int words = dist_gcols_ok(G, K) ? dist_mv_words(A, start, total) : 0;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  const DistinctItem A = M.g.d;
   const uint32_t bw = dist_bitmap_words(A.card);
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
-    const uint32_t sel = dist_mask_word(A, w);
-    if (sel == 0u) continue;
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
-    for (int g = 0; g < K.ngcols; ++g) {
-      const uint32_t* __restrict__ gf = G.g[g].fwd;
-      const int32_t* __restrict__ rm = G.g[g].remap;
-      const int gb = G.g[g].bits;
-      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
-      if (dense) {
-#pragma unroll 8
-        for (int j = 0; j < 32; ++j) {
-          const uint32_t on = 0u - ((sel >> j) & 1u);
-          const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
-        }
-      } else {
-        for (uint32_t m = sel; m;) {
-          const int j = __builtin_ctz(m);
-          m &= m - 1u;
-          const uint32_t id = hll_value(gf, d0 + j, gb);
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
-        }
-      }
-    }
-    for (uint32_t m = sel; m;) {
-      const int j = __builtin_ctz(m);
-      m &= m - 1u;
-      const uint32_t s = mine[j * kHllBlock];
-      if (s >= slots32) continue;  // (a key outside the planned space: the doc marks nothing)
-      dist_mv_range(A.out + static_cast<size_t>(s) * bw, A, total, start[d0 + j], start[d0 + j + 1]);
-    }
-  }
+  sel_mv_group_walk(A, M.g.g, K, M.start, M.total, slot_of,
+                    [&](uint32_t s, auto n, uint32_t lo, uint32_t hi) PGX_SEL_OP {
+                      dist_mv_batch<decltype(n)::value>(A.out + static_cast<size_t>(s) * bw, A, lo, hi);
+                    });
 }
 
 // ---- the result's rows: sizes, then hash codes in dictId order -------------------------------------------------------
@@ -444,87 +328,45 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_emit(const uint32_t* _
 
 }  // namespace pgx
 
-static bool dist_item_ok(const pgx::DistinctItem& d) {
-  return d.num_docs >= 0 && d.bits >= 1 && d.bits <= 32 && d.card >= 1 && d.sel && d.fwd && d.out;
-}
-static bool dist_grid_ok(int nitems, int wgs_per_item) {
-  return nitems >= 0 && nitems <= 65535 && wgs_per_item >= 1 && wgs_per_item <= 1024;
-}
-static bool dist_key_ok(int ngcols, const uint64_t* gmul, int64_t slots) {
-  if (!gmul || ngcols < 1 || ngcols > pgx::kMaxGroupCols || slots < 1 || slots > pgx::kHllMaxGroupSlots) return false;
-  for (int g = 0; g < ngcols; ++g)
-    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return false;  // a mixed-radix layout
-  return true;
-}
-static bool dist_gcols_host_ok(const pgx::DistinctGroupItem& g, int ngcols) {
-  for (int c = 0; c < ngcols; ++c)
-    if (!g.g[c].fwd || g.g[c].bits < 1 || g.g[c].bits > 32) return false;
-  return true;
-}
-static pgx::HllGroupKey dist_key(int ngcols, const uint64_t* gmul, int64_t slots) {
-  pgx::HllGroupKey K{};
-  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
-  K.slots = static_cast<uint64_t>(slots);
-  K.ngcols = ngcols;
-  return K;
-}
+static bool dist_item_ok(const pgx::DistinctItem& d) { return pgx::sel_item_ok(d, 1); }
 
 // items: nitems descriptors in device memory; check: the caller's host copy of them, which is what gets validated.
 // Every item's `out` holds (card + 31) / 32 words (the group forms: slots rows of them), zeroed or holding earlier marks.
 extern "C" hipError_t pgx_launch_distinct_mark(const pgx::DistinctItem* items, const pgx::DistinctItem* check,
                                                int nitems, int wgs_per_item, hipStream_t stream) {
-  if (!dist_grid_ok(nitems, wgs_per_item) || !items || !check) return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!dist_item_ok(check[i])) return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_distinct_mark, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
-                     dim3(pgx::kHllBlock), 0, stream, items, nitems);
-  return hipGetLastError();
+  return pgx::sel_launch(pgx::pgx_distinct_mark, items, check, nitems, wgs_per_item, stream, dist_item_ok);
 }
 
 extern "C" hipError_t pgx_launch_distinct_mark_group(const pgx::DistinctGroupItem* items,
                                                      const pgx::DistinctGroupItem* check, int nitems, int ngcols,
                                                      const uint64_t* gmul, int64_t slots, int wgs_per_item,
                                                      hipStream_t stream) {
-  if (!dist_grid_ok(nitems, wgs_per_item) || !items || !check || !dist_key_ok(ngcols, gmul, slots))
-    return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!dist_item_ok(check[i].d) || !dist_gcols_host_ok(check[i], ngcols)) return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_distinct_mark_group,
-                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kHllBlock), 0,
-                     stream, items, nitems, dist_key(ngcols, gmul, slots));
-  return hipGetLastError();
+  if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
+  return pgx::sel_launch(
+      pgx::pgx_distinct_mark_group, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::DistinctGroupItem& g) { return dist_item_ok(g.d) && pgx::sel_gcols_host_ok(g.g, ngcols); },
+      pgx::sel_key(ngcols, gmul, slots));
 }
 
 // The start arrays are device data, so the kernels clamp every value range to `total`.
 extern "C" hipError_t pgx_launch_distinct_mark_mv(const pgx::DistinctMvItem* items, const pgx::DistinctMvItem* check,
                                                   int nitems, int wgs_per_item, hipStream_t stream) {
-  if (!dist_grid_ok(nitems, wgs_per_item) || !items || !check) return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!dist_item_ok(check[i].d) || !check[i].start || check[i].total < 0) return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_distinct_mark_mv,
-                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kHllBlock), 0,
-                     stream, items, nitems);
-  return hipGetLastError();
+  return pgx::sel_launch(
+      pgx::pgx_distinct_mark_mv, items, check, nitems, wgs_per_item, stream,
+      [](const pgx::DistinctMvItem& m) { return dist_item_ok(m.d) && pgx::sel_mv_ok(m.start, m.total); });
 }
 
 extern "C" hipError_t pgx_launch_distinct_mark_mv_group(const pgx::DistinctMvGroupItem* items,
                                                         const pgx::DistinctMvGroupItem* check, int nitems, int ngcols,
                                                         const uint64_t* gmul, int64_t slots, int wgs_per_item,
                                                         hipStream_t stream) {
-  if (!dist_grid_ok(nitems, wgs_per_item) || !items || !check || !dist_key_ok(ngcols, gmul, slots))
-    return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!dist_item_ok(check[i].g.d) || !dist_gcols_host_ok(check[i].g, ngcols) || !check[i].start ||
-        check[i].total < 0)
-      return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_distinct_mark_mv_group,
-                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kHllBlock), 0,
-                     stream, items, nitems, dist_key(ngcols, gmul, slots));
-  return hipGetLastError();
+  if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
+  return pgx::sel_launch(
+      pgx::pgx_distinct_mark_mv_group, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::DistinctMvGroupItem& m) {
+        return dist_item_ok(m.g.d) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
+      },
+      pgx::sel_key(ngcols, gmul, slots));
 }
 
 // table: slots rows of (card + 31) / 32 words; rows: nrows row indexes (int64, device); counts: nrows u32 (device).

@@ -1,4 +1,6 @@
-// libpgx: DISTINCTCOUNTHLL -- the per-dictId code tables, the runner and the register accessor.
+// libpgx: DISTINCTCOUNTHLL -- the per-dictId tables (HLL codes, DISTINCTCOUNT hash codes: dict_table), the runner and
+// the register accessor.  The runner's items for the offer kernels and pgx_distinct.cpp's for the mark kernels are both
+// built, uploaded and launched by SelItems (pgx_host.h) over one SelScan.
 // DistinctCountHLLAggregationFunction (operator/aggregation/function/DistinctCountHLLAggregationFunction.java:51-92)
 // offers (int) hashCode of every selected doc's value to a stream-lib HyperLogLog(log2m = 8); the executor hands it
 // DataFetcher.getSVHashCodeArray (common/DataFetcher.java:242-248: dictionary.get(dictId).hashCode()).  The kernels
@@ -41,32 +43,30 @@ static int32_t dict_hash_code(const StagedColumn& c, int i) {
   }
 }
 
-// The column's code table in HBM, built on the first query that names it.  Numeric dictionaries share it through
-// their SharedDict (keyed by type and content); a STRING column keeps its own.  Both belong to one staged dictionary:
-// a realtime snapshot stages its (grown) dictionaries afresh and so never sees an earlier table.
-static const uint16_t* hll_code_table(pgx_ctx* ctx, const StagedColumn& c) {
+// A table with one entry per dictId in HBM (entry i: of(the hash code of value i)), built on the first query that
+// needs it.  Numeric dictionaries share it through their SharedDict (keyed by type and content); a STRING column keeps
+// its own: buf is the one or the other.  Both belong to one staged dictionary: a realtime snapshot stages its (grown)
+// dictionaries afresh and so never sees an earlier table.
+template <class T, class F>
+static const T* dict_table(pgx_ctx* ctx, const StagedColumn& c, DevBuf& buf, const char* what, F of) {
   std::lock_guard<std::mutex> g(ctx->dict_mu);
-  DevBuf& buf = c.shared ? c.shared->hll_codes : c.hll_codes;
-  if (buf.p) return buf.as<uint16_t>();
-  std::vector<uint16_t> codes(size_t(std::max(c.card, 1)), 0);
-  for (int i = 0; i < c.card; ++i) codes[size_t(i)] = hll_code(dict_hash_code(c, i));
-  DevBuf b(ctx, codes.size() * 2);
-  hip_check(hipMemcpy(b.p, codes.data(), codes.size() * 2, hipMemcpyHostToDevice), "HLL codes H2D");
+  if (buf.p) return buf.as<T>();
+  std::vector<T> t(size_t(std::max(c.card, 1)), 0);
+  for (int i = 0; i < c.card; ++i) t[size_t(i)] = of(dict_hash_code(c, i));
+  DevBuf b(ctx, t.size() * sizeof(T));
+  hip_check(hipMemcpy(b.p, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice), what);
   buf = std::move(b);
-  return buf.as<uint16_t>();
+  return buf.as<T>();
 }
 
-// DISTINCTCOUNT: the i32 hash code per dictId, kept beside the HLL codes and built the same way.
+static const uint16_t* hll_code_table(pgx_ctx* ctx, const StagedColumn& c) {
+  return dict_table<uint16_t>(ctx, c, c.shared ? c.shared->hll_codes : c.hll_codes, "HLL codes H2D", hll_code);
+}
+
+// DISTINCTCOUNT: the i32 hash code per dictId, kept beside the HLL codes.
 const int32_t* distinct_hash_table(pgx_ctx* ctx, const StagedColumn& c) {
-  std::lock_guard<std::mutex> g(ctx->dict_mu);
-  DevBuf& buf = c.shared ? c.shared->dist_hash : c.dist_hash;
-  if (buf.p) return buf.as<int32_t>();
-  std::vector<int32_t> codes(size_t(std::max(c.card, 1)), 0);
-  for (int i = 0; i < c.card; ++i) codes[size_t(i)] = dict_hash_code(c, i);
-  DevBuf b(ctx, codes.size() * 4);
-  hip_check(hipMemcpy(b.p, codes.data(), codes.size() * 4, hipMemcpyHostToDevice), "DISTINCTCOUNT hash codes H2D");
-  buf = std::move(b);
-  return buf.as<int32_t>();
+  return dict_table<int32_t>(ctx, c, c.shared ? c.shared->dist_hash : c.dist_hash, "DISTINCTCOUNT hash codes H2D",
+                             [](int32_t h) { return h; });
 }
 
 // workgroups per item: at least 4 steps of 256 mask words each, and no more over all items than stay resident
@@ -74,6 +74,35 @@ static int hll_wgs(const pgx_ctx* ctx, int max_words, size_t nitems) {
   int G = std::max(1, (max_words + 4 * kHllBlock - 1) / (4 * kHllBlock));
   G = std::min(G, std::max(1, int(size_t(8 * ctx->num_cus) / std::max<size_t>(1, nitems))));
   return std::min(G, 64);
+}
+
+// The group columns of every segment, once for all the scan's items: forward index, width and, where the segment's
+// dictionary is not the global one, its remap table (a table that segments share is uploaded once).
+static void sel_group_columns(pgx_ctx* ctx, SelScan& S) {
+  std::vector<int32_t> blob;
+  std::map<const std::vector<int32_t>*, size_t> roff;
+  for (int g = 0; g < S.ng; ++g)
+    if (!S.P->gdicts[size_t(g)].identity)
+      for (int s = 0; s < S.n; ++s) {
+        const std::vector<int32_t>* rm = S.P->gdicts[size_t(g)].remap[size_t(s)].get();
+        if (rm && !roff.count(rm)) {
+          roff[rm] = blob.size();
+          blob.insert(blob.end(), rm->begin(), rm->end());
+        }
+      }
+  S.remaps = DevBuf(ctx, std::max<size_t>(1, blob.size()) * 4);
+  if (!blob.empty())
+    hip_check(hipMemcpyAsync(S.remaps.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, S.st), "remap H2D");
+  S.gcols.assign(S.ng > 0 ? size_t(S.n) : 0, SelGCols{});
+  for (size_t s = 0; s < S.gcols.size(); ++s)
+    for (int g = 0; g < S.ng; ++g) {
+      const StagedColumn& gc = S.segs[s]->col(S.q->group_cols[size_t(g)]);
+      HllGCol& c = S.gcols[s].g[g];
+      c.fwd = gc.fwd;  // (a column without one: refused when the first item is built)
+      c.bits = gc.bits;
+      const GlobalDict& gd = S.P->gdicts[size_t(g)];
+      if (!gd.identity && gd.remap[s]) c.remap = S.remaps.as<int32_t>() + roff[gd.remap[s].get()];
+    }
 }
 
 // A query with DISTINCTCOUNTHLL / DISTINCTCOUNTHLLMV functions: the rest of it (its filter, its standard functions or
@@ -173,94 +202,35 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   // 2. the offers, on the same stream: one item per (HLL column, segment)
   DevBuf regs(ctx, std::max<size_t>(1, nh * slots * kHllRegs * 4));
   if (nh) hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
-  std::vector<HllGroupItem> gitems;
-  std::vector<HllItem> items;
-  std::vector<HllMvGroupItem> mgitems;  // DISTINCTCOUNTHLLMV: the same with the docs' value ranges
-  std::vector<HllMvItem> mitems;
-  std::vector<int32_t> blob;
-  std::map<const std::vector<int32_t>*, size_t> roff;
-  for (int g = 0; g < ng; ++g)
-    if (!P.gdicts[size_t(g)].identity)
-      for (int s = 0; s < n; ++s) {
-        const std::vector<int32_t>* rm = P.gdicts[size_t(g)].remap[size_t(s)].get();
-        if (rm && !roff.count(rm)) {
-          roff[rm] = blob.size();
-          blob.insert(blob.end(), rm->begin(), rm->end());
-        }
-      }
-  DevBuf rdev(ctx, std::max<size_t>(1, blob.size()) * 4);
-  if (!blob.empty())
-    hip_check(hipMemcpyAsync(rdev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st), "remap H2D");
+  SelScan S;
+  S.q = &q;
+  S.P = &P;
+  S.segs = segs;
+  S.n = n;
+  S.ng = ng;
+  S.slots = slots;
+  S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size()) * size_t(n));
+  S.scanned = scanned;
+  S.st = st;
+  sel_group_columns(ctx, S);
+  HllItems H;
   for (size_t k = 0; k < nh; ++k)
     for (int s = 0; s < n; ++s) {
       const StagedColumn& col = segs[s]->col(hcols[k]);
       HllItem h{};
-      h.sel = P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)];
-      h.fwd = col.fwd;
       h.codes = hll_code_table(ctx, col);
       h.out = regs.as<uint32_t>() + k * slots * kHllRegs;
-      h.bits = col.bits;
-      h.num_docs = P.ksegs[size_t(s)].num_docs;
       h.ncodes = col.card;
-      if (!h.fwd) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL on a column without a forward index: " + col.name);
-      const int32_t* start = hmv[k] ? col.mv_start.as<const int32_t>() : nullptr;
-      if (hmv[k] && (!start || col.total_entries < 0 || col.total_entries > INT32_MAX))
-        fail(PGX_ERR_INTERNAL, "multi-value column without value ranges: " + col.name);
-      if (ng == 0) {
-        if (hmv[k]) mitems.push_back(HllMvItem{h, start, int32_t(col.total_entries), 0});
-        else items.push_back(h);
-        continue;
-      }
-      HllGroupItem gi{};
-      gi.h = h;
-      for (int g = 0; g < ng; ++g) {
-        const StagedColumn& gc = segs[s]->col(q.group_cols[size_t(g)]);
-        if (!gc.fwd) fail(PGX_ERR_UNSUPPORTED, "GROUP BY a column without a forward index: " + gc.name);
-        gi.g[g].fwd = gc.fwd;
-        gi.g[g].bits = gc.bits;
-        const GlobalDict& gd = P.gdicts[size_t(g)];
-        if (!gd.identity && gd.remap[size_t(s)]) gi.g[g].remap = rdev.as<int32_t>() + roff[gd.remap[size_t(s)].get()];
-      }
-      if (hmv[k]) mgitems.push_back(HllMvGroupItem{gi, start, int32_t(col.total_entries), 0});
-      else gitems.push_back(gi);
+      H.add(S, s, col, hmv[k], "DISTINCTCOUNTHLL", h);
     }
-  const size_t nitems = ng == 0 ? items.size() : gitems.size();
-  const size_t isize = ng == 0 ? sizeof(HllItem) : sizeof(HllGroupItem);
-  const void* ihost = ng == 0 ? static_cast<const void*>(items.data()) : static_cast<const void*>(gitems.data());
-  DevBuf idev(ctx, std::max<size_t>(1, nitems) * isize);
-  if (nitems) hip_check(hipMemcpyAsync(idev.p, ihost, nitems * isize, hipMemcpyHostToDevice, st), "HLL items H2D");
-  const size_t nmv = ng == 0 ? mitems.size() : mgitems.size();
-  const size_t msize = ng == 0 ? sizeof(HllMvItem) : sizeof(HllMvGroupItem);
-  const void* mhost = ng == 0 ? static_cast<const void*>(mitems.data()) : static_cast<const void*>(mgitems.data());
-  DevBuf mdev(ctx, std::max<size_t>(1, nmv) * msize);
-  if (nmv) hip_check(hipMemcpyAsync(mdev.p, mhost, nmv * msize, hipMemcpyHostToDevice, st), "HLL MV items H2D");
-  const int G = hll_wgs(ctx, max_words, nitems + nmv + D.cols.size() * size_t(n));
-  // the single-value and the multi-value items: one launch each, on the same stream, into their own register blocks
-  if (scanned && nmv) {
-    if (ng == 0) {
-      PGX_LAUNCH(st, "pgx_hll_offer_mv",
-                 pgx_launch_hll_offer_mv(mdev.as<HllMvItem>(), mitems.data(), int(nmv), G, st), "HLL MV offers");
-    } else {
-      PGX_LAUNCH(st, "pgx_hll_offer_mv_group",
-                 pgx_launch_hll_offer_mv_group(mdev.as<HllMvGroupItem>(), mgitems.data(), int(nmv), ng, K.gmul,
-                                               int64_t(slots), G, st),
-                 "HLL MV group offers");
-    }
-  }
-  if (scanned && nitems) {
-    if (ng == 0) {
-      PGX_LAUNCH(st, "pgx_hll_offer", pgx_launch_hll_offer(idev.as<HllItem>(), items.data(), int(nitems), G, st),
-                 "HLL offers");
-    } else {
-      PGX_LAUNCH(st, "pgx_hll_offer_group",
-                 pgx_launch_hll_offer_group(idev.as<HllGroupItem>(), gitems.data(), int(nitems), ng, K.gmul,
-                                            int64_t(slots), G, st),
-                 "HLL group offers");
-    }
-  }
+  H.upload(ctx, st, "HLL items H2D", "HLL MV items H2D");
+  // the multi-value and the single-value items: one launch each, on the same stream, into their own register blocks
+  H.launch_mv(S, "pgx_hll_offer_mv", pgx_launch_hll_offer_mv, "HLL MV offers", "pgx_hll_offer_mv_group",
+              pgx_launch_hll_offer_mv_group, "HLL MV group offers");
+  H.launch_sv(S, "pgx_hll_offer", pgx_launch_hll_offer, "HLL offers", "pgx_hll_offer_group",
+              pgx_launch_hll_offer_group, "HLL group offers");
   // the DISTINCTCOUNT[MV] marks, on the same stream
-  if (!D.cols.empty())
-    distinct_mark(ctx, q, P, segs, n, slots, rdev.as<int32_t>(), roff, G, scanned, st, D);
+  if (!D.cols.empty()) distinct_mark(ctx, S, D);
   pgx_result Rs;
   finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
 

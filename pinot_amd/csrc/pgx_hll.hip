@@ -27,6 +27,8 @@
 //                        (start[first] .. start[last + 1]), walked in passes of independent accesses.
 //   pgx_hll_offer_mv_group  the same into the slots x 256 table: the slot of a doc from its single-value group columns
 //                        as in pgx_hll_offer_group, every value of the doc into that slot.
+// The walk over the selection bits (mask words, dense and sparse words, runs of docs, the slots of a word's docs) is
+// shared with pgx_distinct.hip and lives in pgx_hll_device.h; here are the offers it is handed, and the launchers.
 // No workgroup waits on another; all stores are plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
 
@@ -34,19 +36,6 @@
 #include "pgx_internal.h"
 
 namespace pgx {
-
-// mask words of an item; an item with a count or width out of range, or an empty code table, has no rows
-__device__ __forceinline__ int hll_words(const HllItem& A) {
-  return A.num_docs > 0 && A.bits >= 1 && A.bits <= 32 && A.ncodes >= 1 ? (A.num_docs + 31) >> 5 : 0;
-}
-
-// mask word w of the item without the bits at and past num_docs (the spare word is never read: w < words)
-__device__ __forceinline__ uint32_t hll_mask_word(const HllItem& A, int64_t w) {
-  uint32_t sel = A.sel[w];
-  const int32_t left = A.num_docs - static_cast<int32_t>(w * 32);
-  if (left < 32) sel &= (1u << left) - 1u;
-  return sel;
-}
 
 // regs: 256 u32 registers (LDS or HBM)
 __device__ __forceinline__ void hll_offer(uint32_t* regs, const HllItem& A, uint32_t id) {
@@ -78,47 +67,28 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer(const HllItem* __rest
   regs[tid] = 0u;
   __syncthreads();
   const HllItem A = items[item];
-  const int words = hll_words(A);
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
-    const uint32_t sel = hll_mask_word(A, w);
-    if (sel == 0u) continue;
-    if (__builtin_popcount(sel) >= kHllDenseRows) {
-      // three passes over the word, each of 32 independent accesses the hardware keeps in flight together (a chain
-      // of gather, register read and compare per row leaves one access in flight per wave): the codes (entry 0 stands
-      // in for rows that offer nothing, so no load is conditional; a code is never 0), the registers, the few atomics
-      uint32_t v[32];
-      hll_decode_word(A.bits, A.fwd, w, v);
-      hll_gather_codes(A, sel, v);
+  // v: a word's rows.  Out here on purpose: declared inside the callable, where its lifetime ends with every word, the
+  // compiler schedules the passes into 114 VGPRs (4 waves per SIMD) instead of 79 (6).
+  uint32_t v[32];
+  sel_walk(
+      A, sel_words(A),
+      [&](int64_t w, uint32_t sel) PGX_SEL_OP {
+        // three passes over the word, each of 32 independent accesses the hardware keeps in flight together (a chain
+        // of gather, register read and compare per row leaves one access in flight per wave): the codes (entry 0
+        // stands in for rows that offer nothing, so no load is conditional; a code is never 0), the registers, the few
+        // atomics
+        hll_decode_word(A.bits, A.fwd, w, v);
+        hll_gather_codes(A, sel, v);
 #pragma unroll
-      for (int j = 0; j < 32; ++j) v[j] = regs[v[j] >> 8] < (v[j] & 0xFFu) ? v[j] : 0u;
+        for (int j = 0; j < 32; ++j) v[j] = regs[v[j] >> 8] < (v[j] & 0xFFu) ? v[j] : 0u;
 #pragma unroll
-      for (int j = 0; j < 32; ++j)
-        if (v[j] != 0u) atomicMax(&regs[v[j] >> 8], v[j] & 0xFFu);
-    } else {
-      const int32_t d0 = static_cast<int32_t>(w * 32);
-      for (uint32_t m = sel; m;) {
-        const int k = __builtin_ctz(m);
-        m &= m - 1u;
-        hll_offer(regs, A, hll_value(A.fwd, d0 + k, A.bits));
-      }
-    }
-  }
+        for (int j = 0; j < 32; ++j)
+          if (v[j] != 0u) atomicMax(&regs[v[j] >> 8], v[j] & 0xFFu);
+      },
+      [&](int32_t row) PGX_SEL_OP { hll_offer(regs, A, hll_value(A.fwd, row, A.bits)); });
   __syncthreads();
   const uint32_t r = regs[tid];
   if (r != 0u && A.out[tid] < r) atomicMax(&A.out[tid], r);
-}
-
-__device__ __forceinline__ void hll_offer_slot(const HllGroupItem& G, const HllGroupKey& K, int32_t row, uint32_t id) {
-  uint64_t slot = 0;
-  for (int g = 0; g < K.ngcols; ++g) {
-    int64_t gid = hll_value(G.g[g].fwd, row, G.g[g].bits);
-    if (G.g[g].remap) gid = G.g[g].remap[gid];
-    if (gid < 0) return;
-    slot += static_cast<uint64_t>(gid) * K.gmul[g];
-  }
-  if (slot >= K.slots) return;  // (a key outside the planned space: never written)
-  hll_offer(G.h.out + slot * kHllRegs, G.h, id);
 }
 
 // Rows J0 .. J0 + 15 of a mask word whose codes are gathered (v): slots, registers, atomics.  Half a word at a time:
@@ -167,33 +137,25 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
   if (item >= nitems) return;
   const HllGroupItem& G = items[item];
   const HllItem A = G.h;
-  const int tid = static_cast<int>(threadIdx.x);
-  int words = hll_words(A);
-  for (int g = 0; g < K.ngcols; ++g)
-    if (G.g[g].bits < 1 || G.g[g].bits > 32) words = 0;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
-    const uint32_t sel = hll_mask_word(A, w);
-    if (sel == 0u) continue;
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    if (__builtin_popcount(sel) >= kHllDenseRows) {
-      // passes of 32 independent accesses, as in pgx_hll_offer: the codes; per group column the rows' ids (the word's
-      // rows all lie inside the padded index, so the id loads are unconditional; a row that offers nothing takes
-      // remap entry 0) folded into the slot, which shares the word with the code (both fit 16 bits); the registers;
-      // the few atomics
-      uint32_t v[32];
-      hll_decode_word(A.bits, A.fwd, w, v);
-      hll_gather_codes(A, sel, v);
-      hll_group_rows<0>(G, K, d0, v);
-      hll_group_rows<16>(G, K, d0, v);
-    } else {
-      for (uint32_t m = sel; m;) {
-        const int k = __builtin_ctz(m);
-        m &= m - 1u;
-        hll_offer_slot(G, K, d0 + k, hll_value(A.fwd, d0 + k, A.bits));
-      }
-    }
-  }
+  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  sel_walk(
+      A, sel_gcols_ok(G.g, K) ? sel_words(A) : 0,
+      [&](int64_t w, uint32_t sel) PGX_SEL_OP {
+        // passes of 32 independent accesses, as in pgx_hll_offer: the codes; per group column the rows' ids (the word's
+        // rows all lie inside the padded index, so the id loads are unconditional; a row that offers nothing takes
+        // remap entry 0) folded into the slot, which shares the word with the code (both fit 16 bits); the registers;
+        // the few atomics
+        uint32_t v[32];
+        hll_decode_word(A.bits, A.fwd, w, v);
+        hll_gather_codes(A, sel, v);
+        hll_group_rows<0>(G, K, static_cast<int32_t>(w * 32), v);
+        hll_group_rows<16>(G, K, static_cast<int32_t>(w * 32), v);
+      },
+      [&](int32_t row) PGX_SEL_OP {
+        const uint32_t s = sel_row_slot(G.g, K, row);
+        if (s < slots32)  // (a key outside the planned space: never written)
+          hll_offer(A.out + static_cast<size_t>(s) * kHllRegs, A, hll_value(A.fwd, row, A.bits));
+      });
 }
 
 // ---- DISTINCTCOUNTHLLMV: every value of every selected doc ----------------------------------------------------------
@@ -206,7 +168,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
 template <int N>
 __device__ __forceinline__ void hll_mv_batch(uint32_t* regs, const HllItem& A, uint32_t lo, uint32_t hi) {
   uint32_t v[N], m[N];
-  const uint32_t nc = static_cast<uint32_t>(A.ncodes);  // >= 1 (hll_words)
+  const uint32_t nc = static_cast<uint32_t>(A.ncodes);  // >= 1 (sel_words)
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     const uint32_t r = lo + static_cast<uint32_t>(i);
@@ -225,27 +187,7 @@ __device__ __forceinline__ void hll_mv_batch(uint32_t* regs, const HllItem& A, u
     if (v[i] != 0u) atomicMax(&regs[v[i] >> 8], v[i] & 0xFFu);
 }
 
-constexpr int kHllMvBatch = 16;  // value rows per pass of a long range
-constexpr int kHllMvShort = 4;   // ... of a range's last rows (a sparse word's doc has a few values only)
-
-// value rows [lo, hi) clamped to the stream: start[] is device data nobody validated
-__device__ __forceinline__ void hll_mv_range(uint32_t* regs, const HllItem& A, int32_t total, int32_t lo, int32_t hi) {
-  uint32_t a = static_cast<uint32_t>(lo < 0 ? 0 : lo);
-  const uint32_t b = static_cast<uint32_t>(hi < 0 ? 0 : hi < total ? hi : total);  // total > 0 (hll_mv_words)
-  while (a < b && b - a > static_cast<uint32_t>(kHllMvShort)) {
-    hll_mv_batch<kHllMvBatch>(regs, A, a, b);
-    a += kHllMvBatch;
-  }
-  if (a < b) hll_mv_batch<kHllMvShort>(regs, A, a, b);
-}
-
-__device__ __forceinline__ int hll_mv_words(const HllItem& A, const int32_t* start, int32_t total) {
-  return start && total > 0 ? hll_words(A) : 0;
-}
-
-// A maximal run of selected docs a .. a + len - 1 of a mask word owns one contiguous value range: ranges are walked,
-// not docs, and a fully selected word is one range.  One lane walks a range alone (long ranges are not shared across
-// the wave), so a doc with hundreds of values keeps its lane busy while the wave's other lanes wait.
+// A run of consecutive selected docs owns one contiguous range of the value stream (sel_mv_walk).
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv(const HllMvItem* __restrict__ items, int nitems) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
@@ -255,81 +197,26 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv(const HllMvItem* _
   __syncthreads();
   const HllMvItem M = items[item];
   const HllItem A = M.h;
-  const int words = hll_mv_words(A, M.start, M.total);
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    for (uint32_t m = hll_mask_word(A, w); m;) {  // (bits at and past num_docs are off: d0 + a + len <= num_docs)
-      const int a = __builtin_ctz(m);
-      const uint32_t rest = ~(m >> a);
-      const int len = rest ? __builtin_ctz(rest) : 32;
-      m &= ~((len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u)) << a);
-      hll_mv_range(regs, A, M.total, M.start[d0 + a], M.start[d0 + a + len]);
-    }
-  }
+  sel_mv_walk(A, sel_mv_words(A, M.start, M.total), M.start, M.total, [&](auto n, uint32_t lo, uint32_t hi) PGX_SEL_OP {
+    hll_mv_batch<decltype(n)::value>(regs, A, lo, hi);
+  });
   __syncthreads();
   const uint32_t r = regs[tid];
   if (r != 0u && A.out[tid] < r) atomicMax(&A.out[tid], r);
 }
 
-// The same over a table of slots x 256 registers in HBM.  A doc's slot comes from its single-value group columns as in
-// pgx_hll_offer_group; every value of the doc goes to that slot, so ranges are walked per doc.  A word's slots are
-// computed first, for a dense word in passes of independent loads over its 32 docs (all inside the group columns'
-// padded indexes; a doc that is not selected takes remap entry 0), and parked in LDS: one column of 32 per thread,
-// which only that thread touches.
+// The same over a table of slots x 256 registers in HBM: every value of a doc into the doc's slot (sel_mv_group_walk).
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv_group(const HllMvGroupItem* __restrict__ items,
                                                                     int nitems, const HllGroupKey K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t slot_of[32 * kHllBlock];
   const HllMvGroupItem& M = items[item];
-  const HllGroupItem& G = M.g;
-  const HllItem A = G.h;
-  const int32_t* __restrict__ start = M.start;
-  const int32_t total = M.total;
-  const int tid = static_cast<int>(threadIdx.x);
-  uint32_t* const mine = slot_of + tid;  // doc j of the word: mine[j * kHllBlock]
-  int words = hll_mv_words(A, start, total);
-  for (int g = 0; g < K.ngcols; ++g)
-    if (G.g[g].bits < 1 || G.g[g].bits > 32) words = 0;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
-  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
-    const uint32_t sel = hll_mask_word(A, w);
-    if (sel == 0u) continue;
-    const int32_t d0 = static_cast<int32_t>(w * 32);
-    const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
-    for (int g = 0; g < K.ngcols; ++g) {
-      const uint32_t* __restrict__ gf = G.g[g].fwd;
-      const int32_t* __restrict__ rm = G.g[g].remap;
-      const int gb = G.g[g].bits;
-      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
-      if (dense) {
-#pragma unroll 8
-        for (int j = 0; j < 32; ++j) {
-          const uint32_t on = 0u - ((sel >> j) & 1u);
-          const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
-        }
-      } else {
-        for (uint32_t m = sel; m;) {
-          const int j = __builtin_ctz(m);
-          m &= m - 1u;
-          const uint32_t id = hll_value(gf, d0 + j, gb);
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
-        }
-      }
-    }
-    for (uint32_t m = sel; m;) {
-      const int j = __builtin_ctz(m);
-      m &= m - 1u;
-      const uint32_t s = mine[j * kHllBlock];
-      if (s >= slots32) continue;  // (a key outside the planned space: the doc offers nothing)
-      hll_mv_range(A.out + static_cast<size_t>(s) * kHllRegs, A, total, start[d0 + j], start[d0 + j + 1]);
-    }
-  }
+  const HllItem A = M.g.h;
+  sel_mv_group_walk(A, M.g.g, K, M.start, M.total, slot_of,
+                    [&](uint32_t s, auto n, uint32_t lo, uint32_t hi) PGX_SEL_OP {
+                      hll_mv_batch<decltype(n)::value>(A.out + static_cast<size_t>(s) * kHllRegs, A, lo, hi);
+                    });
 }
 
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_narrow(const uint32_t* __restrict__ table,
@@ -350,46 +237,23 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_narrow(const uint32_t* __re
 
 }  // namespace pgx
 
-static bool hll_item_ok(const pgx::HllItem& h) {
-  return h.num_docs >= 0 && h.bits >= 1 && h.bits <= 32 && h.ncodes >= 0 && h.sel && h.fwd && h.codes && h.out;
-}
+static bool hll_item_ok(const pgx::HllItem& h) { return pgx::sel_item_ok(h, 0) && h.codes; }
 
 // items: nitems descriptors in device memory; check: the caller's host copy of them, which is what gets validated.
 extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx::HllItem* check, int nitems,
                                            int wgs_per_item, hipStream_t stream) {
-  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check)
-    return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!hll_item_ok(check[i])) return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_hll_offer, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
-                     dim3(pgx::kHllBlock), 0, stream, items, nitems);
-  return hipGetLastError();
+  return pgx::sel_launch(pgx::pgx_hll_offer, items, check, nitems, wgs_per_item, stream, hll_item_ok);
 }
 
 // Every item's `h.out` is a table of slots x 256 u32 registers, zeroed by the caller.  gmul: ngcols host values.
 extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
                                                  int nitems, int ngcols, const uint64_t* gmul, int64_t slots,
                                                  int wgs_per_item, hipStream_t stream) {
-  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check || !gmul)
-    return hipErrorInvalidValue;
-  if (ngcols < 1 || ngcols > pgx::kMaxGroupCols || slots < 1 || slots > pgx::kHllMaxGroupSlots)
-    return hipErrorInvalidValue;
-  for (int g = 0; g < ngcols; ++g)
-    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return hipErrorInvalidValue;  // a mixed-radix layout
-  for (int i = 0; i < nitems; ++i) {
-    if (!hll_item_ok(check[i].h)) return hipErrorInvalidValue;
-    for (int g = 0; g < ngcols; ++g)
-      if (!check[i].g[g].fwd || check[i].g[g].bits < 1 || check[i].g[g].bits > 32) return hipErrorInvalidValue;
-  }
-  if (nitems == 0) return hipSuccess;
-  pgx::HllGroupKey K{};
-  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
-  K.slots = static_cast<uint64_t>(slots);
-  K.ngcols = ngcols;
-  hipLaunchKernelGGL(pgx::pgx_hll_offer_group, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
-                     dim3(pgx::kHllBlock), 0, stream, items, nitems, K);
-  return hipGetLastError();
+  if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
+  return pgx::sel_launch(
+      pgx::pgx_hll_offer_group, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::HllGroupItem& g) { return hll_item_ok(g.h) && pgx::sel_gcols_host_ok(g.g, ngcols); },
+      pgx::sel_key(ngcols, gmul, slots));
 }
 
 // out: ngroups x 256 bytes (as ngroups x 64 dwords); group i's registers are those of table slot slot[i].
@@ -408,14 +272,9 @@ extern "C" hipError_t pgx_launch_hll_narrow(const uint32_t* table, const int64_t
 // itself is device data, so the kernels clamp every value range to `total`.
 extern "C" hipError_t pgx_launch_hll_offer_mv(const pgx::HllMvItem* items, const pgx::HllMvItem* check, int nitems,
                                               int wgs_per_item, hipStream_t stream) {
-  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check)
-    return hipErrorInvalidValue;
-  for (int i = 0; i < nitems; ++i)
-    if (!hll_item_ok(check[i].h) || !check[i].start || check[i].total < 0) return hipErrorInvalidValue;
-  if (nitems == 0) return hipSuccess;
-  hipLaunchKernelGGL(pgx::pgx_hll_offer_mv, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
-                     dim3(pgx::kHllBlock), 0, stream, items, nitems);
-  return hipGetLastError();
+  return pgx::sel_launch(
+      pgx::pgx_hll_offer_mv, items, check, nitems, wgs_per_item, stream,
+      [](const pgx::HllMvItem& m) { return hll_item_ok(m.h) && pgx::sel_mv_ok(m.start, m.total); });
 }
 
 // Every item's `g.h.out` is a table of slots x 256 u32 registers, zeroed by the caller.  gmul: ngcols host values.
@@ -423,24 +282,11 @@ extern "C" hipError_t pgx_launch_hll_offer_mv_group(const pgx::HllMvGroupItem* i
                                                     const pgx::HllMvGroupItem* check, int nitems, int ngcols,
                                                     const uint64_t* gmul, int64_t slots, int wgs_per_item,
                                                     hipStream_t stream) {
-  if (nitems < 0 || nitems > 65535 || wgs_per_item < 1 || wgs_per_item > 1024 || !items || !check || !gmul)
-    return hipErrorInvalidValue;
-  if (ngcols < 1 || ngcols > pgx::kMaxGroupCols || slots < 1 || slots > pgx::kHllMaxGroupSlots)
-    return hipErrorInvalidValue;
-  for (int g = 0; g < ngcols; ++g)
-    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return hipErrorInvalidValue;  // a mixed-radix layout
-  for (int i = 0; i < nitems; ++i) {
-    if (!hll_item_ok(check[i].g.h) || !check[i].start || check[i].total < 0) return hipErrorInvalidValue;
-    for (int g = 0; g < ngcols; ++g)
-      if (!check[i].g.g[g].fwd || check[i].g.g[g].bits < 1 || check[i].g.g[g].bits > 32) return hipErrorInvalidValue;
-  }
-  if (nitems == 0) return hipSuccess;
-  pgx::HllGroupKey K{};
-  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
-  K.slots = static_cast<uint64_t>(slots);
-  K.ngcols = ngcols;
-  hipLaunchKernelGGL(pgx::pgx_hll_offer_mv_group,
-                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kHllBlock), 0,
-                     stream, items, nitems, K);
-  return hipGetLastError();
+  if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
+  return pgx::sel_launch(
+      pgx::pgx_hll_offer_mv_group, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::HllMvGroupItem& m) {
+        return hll_item_ok(m.g.h) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
+      },
+      pgx::sel_key(ngcols, gmul, slots));
 }

@@ -1,8 +1,15 @@
-// libpgx: device helpers shared by the kernels that run over the query kernels' selection bits (pgx_hll.hip,
+// libpgx: device code shared by the kernels that run over the query kernels' selection bits (pgx_hll.hip,
 // pgx_distinct.hip): reading rows of a packed big-endian fixed-bit forward index, one at a time or a whole mask word's
-// 32 rows at once, and folding group columns' global ids into a dense slot.
+// 32 rows at once; folding group columns' global ids into a dense slot; and the walk itself -- an item's 32-doc mask
+// words strided over a workgroup, zero words skipped, dense words decoded whole and sparse ones row by row, multi-value
+// columns as runs of docs that own ranges of the value stream, under GROUP BY with the docs' slots parked in LDS.  The
+// walk is a template over the item type; what happens to a word, a row or a batch of value rows is the caller's
+// callable, so nothing here knows whether it maxes a register or ORs a presence bit.  The launchers' argument checks
+// are at the end.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "pgx_internal.h"
 
@@ -82,6 +89,204 @@ __device__ __forceinline__ uint32_t hll_mv_fold(uint32_t prev, uint32_t gid, uin
   const uint32_t bad = static_cast<uint32_t>(static_cast<int32_t>(hi | (0u - hi)) >> 31);
   const uint32_t term = __builtin_elementwise_min((gid & 0xFFFFu) * mul, 0x10000u);  // mul <= 0x10000 (launcher)
   return (__builtin_elementwise_min(prev, 0x10000u) + term) | (bad & kHllNoSlot);
+}
+
+// the slot of one row, or kHllNoSlot or more: a remap of -1, or a key outside the planned space
+__device__ __forceinline__ uint32_t sel_row_slot(const HllGCol* gc, const HllGroupKey& K, int32_t row) {
+  uint32_t s = 0u;
+  for (int g = 0; g < K.ngcols; ++g) {
+    const uint32_t id = hll_value(gc[g].fwd, row, gc[g].bits);
+    const uint32_t gid = gc[g].remap ? static_cast<uint32_t>(gc[g].remap[id]) : id;  // a negative id: >= 2^31
+    s = hll_mv_fold(s, gid, static_cast<uint32_t>(K.gmul[g]));
+  }
+  return s;
+}
+
+__device__ __forceinline__ bool sel_gcols_ok(const HllGCol* gc, const HllGroupKey& K) {
+  bool ok = true;
+  for (int g = 0; g < K.ngcols; ++g) ok = ok && gc[g].bits >= 1 && gc[g].bits <= 32;
+  return ok;
+}
+
+// ---- the walk over an item's selection bits --------------------------------------------------------------------------
+// On every callable handed to a walk: inlined before anything is optimised, as the loops written out by hand were.
+// (Left to the inliner's judgement, pgx_distinct_mark_mv kept its item in scratch memory.)
+#define PGX_SEL_OP __attribute__((always_inline))
+
+// the item's limit: dictIds at or past it take no part
+__host__ __device__ __forceinline__ int32_t sel_limit(const HllItem& A) { return A.ncodes; }
+__host__ __device__ __forceinline__ int32_t sel_limit(const DistinctItem& A) { return A.card; }
+
+// mask words of an item; an item with a count or width out of range, or an empty code table or dictionary, has no rows
+template <class Item>
+__device__ __forceinline__ int sel_words(const Item& A) {
+  return A.num_docs > 0 && A.bits >= 1 && A.bits <= 32 && sel_limit(A) >= 1 ? (A.num_docs + 31) >> 5 : 0;
+}
+template <class Item>
+__device__ __forceinline__ int sel_mv_words(const Item& A, const int32_t* start, int32_t total) {
+  return start && total > 0 ? sel_words(A) : 0;
+}
+
+// mask word w of the item without the bits at and past num_docs (the spare word is never read: w < words)
+template <class Item>
+__device__ __forceinline__ uint32_t sel_mask_word(const Item& A, int64_t w) {
+  uint32_t sel = A.sel[w];
+  const int32_t left = A.num_docs - static_cast<int32_t>(w * 32);
+  if (left < 32) sel &= (1u << left) - 1u;
+  return sel;
+}
+
+// The workgroup's share of the item's mask words, one word per thread and step.  A word with kHllDenseRows or more
+// selected rows goes to dense(w, sel) whole, the rows of any other non-zero word one by one to row(doc).
+template <class Item, class Dense, class Row>
+__device__ __forceinline__ void sel_walk(const Item& A, int words, Dense dense, Row row) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x; w < words; w += stride) {
+    const uint32_t sel = sel_mask_word(A, w);
+    if (sel == 0u) continue;
+    if (__builtin_popcount(sel) >= kHllDenseRows) {
+      dense(w, sel);
+    } else {
+      const int32_t d0 = static_cast<int32_t>(w * 32);
+      for (uint32_t m = sel; m;) {
+        const int k = __builtin_ctz(m);
+        m &= m - 1u;
+        row(d0 + k);
+      }
+    }
+  }
+}
+
+template <int N>
+using sel_rows = std::integral_constant<int, N>;  // a batch's size, handed to the callable as a type: its loops unroll
+constexpr int kSelMvBatch = 16;  // value rows per pass of a long range
+constexpr int kSelMvShort = 4;   // ... of a range's last rows (a sparse word's doc has a few values only)
+
+// value rows [lo, hi) clamped to the stream (start[] is device data nobody validated), handed on as
+// batch(sel_rows<N>, a, b): rows a .. a + N - 1 of which those below b count, a < b <= total
+template <class Batch>
+__device__ __forceinline__ void sel_mv_range(int32_t total, int32_t lo, int32_t hi, Batch batch) {
+  uint32_t a = static_cast<uint32_t>(lo < 0 ? 0 : lo);
+  const uint32_t b = static_cast<uint32_t>(hi < 0 ? 0 : hi < total ? hi : total);  // total > 0 (sel_mv_words)
+  while (a < b && b - a > static_cast<uint32_t>(kSelMvShort)) {
+    batch(sel_rows<kSelMvBatch>{}, a, b);
+    a += kSelMvBatch;
+  }
+  if (a < b) batch(sel_rows<kSelMvShort>{}, a, b);
+}
+
+// A maximal run of selected docs a .. a + len - 1 of a mask word owns one contiguous value range: ranges are walked,
+// not docs, and a fully selected word is one range.  One lane walks a range alone (long ranges are not shared across
+// the wave), so a doc with hundreds of values keeps its lane busy while the wave's other lanes wait.
+template <class Item, class Batch>
+__device__ __forceinline__ void sel_mv_walk(const Item& A, int words, const int32_t* start, int32_t total,
+                                            Batch batch) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x; w < words; w += stride) {
+    const int32_t d0 = static_cast<int32_t>(w * 32);
+    for (uint32_t m = sel_mask_word(A, w); m;) {  // (bits at and past num_docs are off: d0 + a + len <= num_docs)
+      const int a = __builtin_ctz(m);
+      const uint32_t rest = ~(m >> a);
+      const int len = rest ? __builtin_ctz(rest) : 32;
+      m &= ~((len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1u)) << a);
+      sel_mv_range(total, start[d0 + a], start[d0 + a + len], batch);
+    }
+  }
+}
+
+// The same under GROUP BY.  A doc's slot comes from its single-value group columns gc; every value of the doc goes to
+// that slot, so ranges are walked per doc: batch(slot, sel_rows<N>, a, b).  A word's slots are computed first, for a
+// dense word in passes of independent loads over its 32 docs (all inside the group columns' padded indexes; a doc that
+// is not selected takes remap entry 0), and parked in LDS (slot_of: 32 * kHllBlock words): one column of 32 per thread,
+// which only that thread touches.
+template <class Item, class Batch>
+__device__ __forceinline__ void sel_mv_group_walk(const Item& A, const HllGCol* gc, const HllGroupKey& K,
+                                                  const int32_t* __restrict__ start, int32_t total, uint32_t* slot_of,
+                                                  Batch batch) {
+  const int tid = static_cast<int>(threadIdx.x);
+  uint32_t* const mine = slot_of + tid;  // doc j of the word: mine[j * kHllBlock]
+  const int words = sel_gcols_ok(gc, K) ? sel_mv_words(A, start, total) : 0;
+  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
+  for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
+    const uint32_t sel = sel_mask_word(A, w);
+    if (sel == 0u) continue;
+    const int32_t d0 = static_cast<int32_t>(w * 32);
+    const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
+    for (int g = 0; g < K.ngcols; ++g) {
+      const uint32_t* __restrict__ gf = gc[g].fwd;
+      const int32_t* __restrict__ rm = gc[g].remap;
+      const int gb = gc[g].bits;
+      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+      if (dense) {
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j) {
+          const uint32_t on = 0u - ((sel >> j) & 1u);
+          const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
+          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
+          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+        }
+      } else {
+        for (uint32_t m = sel; m;) {
+          const int j = __builtin_ctz(m);
+          m &= m - 1u;
+          const uint32_t id = hll_value(gf, d0 + j, gb);
+          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
+          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+        }
+      }
+    }
+    for (uint32_t m = sel; m;) {
+      const int j = __builtin_ctz(m);
+      m &= m - 1u;
+      const uint32_t s = mine[j * kHllBlock];
+      if (s >= slots32) continue;  // (a key outside the planned space: the doc takes no part)
+      sel_mv_range(total, start[d0 + j], start[d0 + j + 1],
+                   [&](auto n, uint32_t a, uint32_t b) PGX_SEL_OP { batch(s, n, a, b); });
+    }
+  }
+}
+
+// ---- the launchers' checks, on the caller's host copy of the items ----------------------------------------------------
+inline bool sel_grid_ok(int nitems, int wgs_per_item) {
+  return nitems >= 0 && nitems <= 65535 && wgs_per_item >= 1 && wgs_per_item <= 1024;
+}
+inline bool sel_key_ok(int ngcols, const uint64_t* gmul, int64_t slots) {
+  if (!gmul || ngcols < 1 || ngcols > kMaxGroupCols || slots < 1 || slots > kHllMaxGroupSlots) return false;
+  for (int g = 0; g < ngcols; ++g)
+    if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return false;  // a mixed-radix layout
+  return true;
+}
+inline bool sel_gcols_host_ok(const HllGCol* gc, int ngcols) {
+  for (int c = 0; c < ngcols; ++c)
+    if (!gc[c].fwd || gc[c].bits < 1 || gc[c].bits > 32) return false;
+  return true;
+}
+template <class Item>
+bool sel_item_ok(const Item& a, int32_t least_limit) {
+  return a.num_docs >= 0 && a.bits >= 1 && a.bits <= 32 && sel_limit(a) >= least_limit && a.sel && a.fwd && a.out;
+}
+inline bool sel_mv_ok(const int32_t* start, int32_t total) { return start && total >= 0; }
+inline HllGroupKey sel_key(int ngcols, const uint64_t* gmul, int64_t slots) {  // (after sel_key_ok)
+  HllGroupKey K{};
+  for (int g = 0; g < ngcols; ++g) K.gmul[g] = gmul[g];
+  K.slots = static_cast<uint64_t>(slots);
+  K.ngcols = ngcols;
+  return K;
+}
+
+// One launch over nitems items, grid (workgroups per item, items): refused unless the grid is in range, both copies of
+// the items are there and ok(check[i]) holds for every item; no items, no launch.  extra: the group forms' key.
+template <class Item, class Ok, class... Extra>
+hipError_t sel_launch(void (*kernel)(const Item*, int, Extra...), const Item* items, const Item* check, int nitems,
+                      int wgs_per_item, hipStream_t stream, Ok ok, Extra... extra) {
+  if (!sel_grid_ok(nitems, wgs_per_item) || !items || !check) return hipErrorInvalidValue;
+  for (int i = 0; i < nitems; ++i)
+    if (!ok(check[i])) return hipErrorInvalidValue;
+  if (nitems == 0) return hipSuccess;
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(kHllBlock),
+                     0, stream, items, nitems, extra...);
+  return hipGetLastError();
 }
 
 }  // namespace pgx

@@ -1174,6 +1174,103 @@ inline bool query_has_hll(const pgx_query& q) {
   return false;
 }
 
+// ---- the functions over selection bits inside run_hll: the HLL offers (pgx_hll.cpp), the DISTINCTCOUNT marks -------
+// What they share of one scan: where every segment's selection words lie, the group columns of every segment (filled
+// once, with the remap tables' device copy) and the launches' grid.
+struct SelGCols {
+  pgx::HllGCol g[pgx::kMaxGroupCols];
+};
+struct SelScan {
+  const pgx_query* q = nullptr;
+  const ExecPlan* P = nullptr;
+  pgx_segment* const* segs = nullptr;
+  int n = 0, ng = 0;
+  uint64_t slots = 1;
+  int wgs = 1;           // workgroups per item
+  bool scanned = false;  // false: every segment empty, nothing is launched and the outputs stay zero
+  hipStream_t st = nullptr;
+  DevBuf remaps;                // the segments' remap tables, one after the other
+  std::vector<SelGCols> gcols;  // per segment (ng > 0)
+};
+
+// The items of one family (HLL or DISTINCTCOUNT) for one scan: single-value or multi-value column, without or under
+// GROUP BY.  Of each pair of vectors the query's form fills one.  The device copies stay alive with the host copies,
+// until the stream was waited for.
+template <class Item, class GItem, class MvItem, class MvGItem>
+struct SelItems {
+  std::vector<Item> sv;
+  std::vector<GItem> gsv;
+  std::vector<MvItem> mv;
+  std::vector<MvGItem> gmv;
+  DevBuf sdev, mdev;
+
+  // One item for column `col` of segment s.  a: the family's own fields (the output, the table, the limit); the
+  // selection words, the forward index and the counts are filled here.  fn: the function's name for the refusals.
+  void add(const SelScan& S, int s, const StagedColumn& col, bool is_mv, const char* fn, Item a) {
+    a.sel = S.P->sel_buf.template as<uint32_t>() + S.P->sel_off[size_t(s)];
+    a.fwd = col.fwd;
+    a.bits = col.bits;
+    a.num_docs = S.P->ksegs[size_t(s)].num_docs;
+    if (!a.fwd) fail(PGX_ERR_UNSUPPORTED, std::string(fn) + " on a column without a forward index: " + col.name);
+    const int32_t* start = is_mv ? col.mv_start.template as<const int32_t>() : nullptr;
+    if (is_mv && (!start || col.total_entries < 0 || col.total_entries > INT32_MAX))
+      fail(PGX_ERR_INTERNAL, "multi-value column without value ranges: " + col.name);
+    const int32_t total = is_mv ? int32_t(col.total_entries) : 0;
+    if (S.ng == 0) {
+      if (is_mv) mv.push_back(MvItem{a, start, total, 0});
+      else sv.push_back(a);
+      return;
+    }
+    GItem gi{a, {}};
+    for (int g = 0; g < S.ng; ++g) {
+      gi.g[g] = S.gcols[size_t(s)].g[g];
+      if (!gi.g[g].fwd)
+        fail(PGX_ERR_UNSUPPORTED, "GROUP BY a column without a forward index: " + S.q->group_cols[size_t(g)]);
+    }
+    if (is_mv) gmv.push_back(MvGItem{gi, start, total, 0});
+    else gsv.push_back(gi);
+  }
+
+  void upload(pgx_ctx* ctx, hipStream_t st, const char* what, const char* mv_what) {
+    sdev = put(ctx, st, sv, gsv, what);
+    mdev = put(ctx, st, mv, gmv, mv_what);
+  }
+
+  // One launch over the single-value items, one over the multi-value ones: of the plain or of the group kernel.
+  template <class L, class GL>
+  void launch_sv(const SelScan& S, const char* name, L plain, const char* what, const char* gname, GL group,
+                 const char* gwhat) const {
+    run(S, sdev, sv, gsv, name, plain, what, gname, group, gwhat);
+  }
+  template <class L, class GL>
+  void launch_mv(const SelScan& S, const char* name, L plain, const char* what, const char* gname, GL group,
+                 const char* gwhat) const {
+    run(S, mdev, mv, gmv, name, plain, what, gname, group, gwhat);
+  }
+
+ private:
+  template <class A, class B>
+  static DevBuf put(pgx_ctx* ctx, hipStream_t st, const std::vector<A>& a, const std::vector<B>& b, const char* what) {
+    const size_t bytes = a.size() * sizeof(A) + b.size() * sizeof(B);  // (one of the two is empty)
+    const void* host = a.empty() ? static_cast<const void*>(b.data()) : static_cast<const void*>(a.data());
+    DevBuf d(ctx, std::max<size_t>(1, bytes));
+    if (bytes) hip_check(hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, st), what);
+    return d;
+  }
+  template <class A, class B, class L, class GL>
+  static void run(const SelScan& S, const DevBuf& dev, const std::vector<A>& a, const std::vector<B>& b,
+                  const char* name, L plain, const char* what, const char* gname, GL group, const char* gwhat) {
+    if (!S.scanned) return;
+    if (!a.empty()) PGX_LAUNCH(S.st, name, plain(dev.as<A>(), a.data(), int(a.size()), S.wgs, S.st), what);
+    if (!b.empty())
+      PGX_LAUNCH(S.st, gname,
+                 group(dev.as<B>(), b.data(), int(b.size()), S.ng, S.P->kq.gmul, int64_t(S.slots), S.wgs, S.st), gwhat);
+  }
+};
+using HllItems = SelItems<pgx::HllItem, pgx::HllGroupItem, pgx::HllMvItem, pgx::HllMvGroupItem>;
+using DistinctItems =
+    SelItems<pgx::DistinctItem, pgx::DistinctGroupItem, pgx::DistinctMvItem, pgx::DistinctMvGroupItem>;
+
 // ---- pgx_distinct.cpp: DISTINCTCOUNT / DISTINCTCOUNTMV inside run_hll ----------------------------------------------
 // One presence bitmap per (column, distinct dictionary): slots rows of `words` u32.  Segments whose dictionaries are
 // the same (one SharedDict, or equal staged STRING dictionaries) mark one bitmap.
@@ -1188,18 +1285,11 @@ struct DistinctRun {
   std::vector<char> mv;
   std::vector<std::vector<DistinctBitmap>> maps;  // per column
   std::vector<std::vector<int>> map_of;           // per column and segment: its bitmap
-  // the mark kernels' items and their device copies, alive until the stream was waited for
-  std::vector<pgx::DistinctItem> items;
-  std::vector<pgx::DistinctGroupItem> gitems;
-  std::vector<pgx::DistinctMvItem> mitems;
-  std::vector<pgx::DistinctMvGroupItem> mgitems;
-  DevBuf idev, mdev;
+  DistinctItems items;                            // the mark kernels' items
 };
 const int32_t* distinct_hash_table(pgx_ctx* ctx, const StagedColumn& c);  // pgx_hll.cpp, beside the HLL code tables
 void distinct_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots, DistinctRun& D);
-void distinct_mark(pgx_ctx* ctx, const pgx_query& q, const ExecPlan& P, pgx_segment* const* segs, int n, uint64_t slots,
-                   const int32_t* remaps, const std::map<const std::vector<int32_t>*, size_t>& remap_off, int wgs,
-                   bool scanned, hipStream_t st, DistinctRun& D);
+void distinct_mark(pgx_ctx* ctx, const SelScan& S, DistinctRun& D);
 // rows: the table row (slot) of every group of the result, in its order
 void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& rows, uint64_t slots, hipStream_t st,
                       pgx_result* R);

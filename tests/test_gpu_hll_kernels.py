@@ -251,6 +251,33 @@ def test_group_slots(hk, gcards):
     assert (got[:, 255] == 0).all()  # padding rows, bits past num_docs, the spare word
 
 
+@pytest.mark.parametrize("gcards", [(5, 3), (256, 256)])
+def test_group_keys_outside_the_space_offer_nothing(hk, gcards):
+    """A remap entry of -1 in column 0 and global ids at and just past gcards[1] in column 1 (null remap): those rows
+    offer nothing, on the row-by-row path (density 0.05) and the whole-word path (0.9) alike, whatever the grid; the
+    last mask word is partial."""
+    rng = np.random.default_rng(31 + gcards[0])
+    n, slots = 3001, gcards[0] * gcards[1]
+    for density in (0.05, 0.9):
+        it = _group_item(rng, n, density, 12, 4000, gcards, gcards[0])
+        ids0, remap, bits0 = it["g"][0]
+        remap = remap.copy()
+        remap[[1, len(remap) - 1]] = -1             # (every local id stays inside the table)
+        ids1 = it["g"][1][0].copy()
+        past = rng.random(n) < 0.05
+        ids1[past] = gcards[1] + rng.integers(0, 2, int(past.sum()))
+        it["g"] = [(ids0, remap, bits0), (ids1, None, int(gcards[1] + 1).bit_length())]
+        slot = R.group_slots([(ids0, remap), (ids1, None)], (1, gcards[0]))
+        bad = (remap[ids0] < 0) | (ids1 >= gcards[1])
+        assert (bad & it["selected"]).sum() > 2 and ((slot[~bad] >= 0) & (slot[~bad] < slots)).all()
+        pre = np.zeros((slots, R.REGS), np.uint32)
+        exp = R.offer_group(it["selected"] & ~bad, it["ids"], it["codes"], np.where(bad, -1, slot), slots, pre)
+        for wgs in (1, 3):
+            got, _, _ = _run_group(hk, [it], gcards, prefill=pre, wgs=wgs)  # (checks the guard words past the table)
+            np.testing.assert_array_equal(got, exp)
+        assert (got[:, 255] == 0).all() and got.any()
+
+
 def test_group_table_is_maxed_into_and_grid_free(hk):
     rng = np.random.default_rng(21)
     gcards = (7, 5)
