@@ -21,7 +21,7 @@ build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o bui
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_jit.o: $(CSRC)/pgx_jit.cpp $(HDR) build/pgx_jit_abi.inc build/pgx_jit_device.inc
+build/pgx_jit.o: $(CSRC)/pgx_jit.cpp $(HDR) build/pgx_jit_abi.inc build/pgx_roaring_device.inc build/pgx_jit_device.inc
 	$(HIPCC) $(HIPFLAGS) -Ibuild -c $< -o $@
 
 build/pgx_kernels.o: $(CSRC)/pgx_kernels.hip $(HDR)
@@ -52,11 +52,15 @@ build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_in
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+build/pgx_roaring.o: $(CSRC)/pgx_roaring.hip $(CSRC)/pgx_roaring_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 build/pgx_distinct_hip.o: $(CSRC)/pgx_distinct.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o build/pgx_distinct_hip.o build/pgx_distinct.o
+pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o build/pgx_distinct_hip.o build/pgx_distinct.o build/pgx_roaring.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ -L/opt/rocm/lib -lhiprtc -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
 
 # Host-only check of pgx_hash.h (the Java hash codes, the sort + unique union) under AddressSanitizer and UBSan: no device

@@ -56,74 +56,20 @@ void canon_rprog(std::vector<int>& op, std::vector<int>& arg) {
   arg.swap(a2);
 }
 
-// Mask slots the wave-per-chunk kernel (pgx_roaring_program_wave) needs for one program.  While the top operand is
-// "pure" (an OR of leaves, nothing applied yet), a leaf directly followed by OR is ORed into its slot, and a leaf
-// directly followed by NOT, AND is cleared out of it (which ends its purity); every other leaf takes a new slot.
-int rprog_slots(const RProg& r) {
-  std::vector<bool> pure;  // the operand stack's "pure OR of leaves" flags
-  int ns = 0;
-  for (int i = 0; i < r.nops; ++i) {
-    const int op = r.op[i];
-    if (op == RP_LEAF) {
-      const bool top = !pure.empty() && pure.back();
-      const bool f_or = top && i + 1 < r.nops && r.op[i + 1] == RP_OR;
-      const bool f_andnot = top && !f_or && i + 2 < r.nops && r.op[i + 1] == RP_NOT && r.op[i + 2] == RP_AND;
-      if (f_or) {
-        ++i;
-      } else if (f_andnot) {
-        pure.back() = false;
-        i += 2;
-      } else {
-        pure.push_back(true);
-        ++ns;
-      }
-    } else if (op == RP_NOT) {
-      if (!pure.empty()) pure.back() = false;
-    } else if (pure.size() >= 2) {
-      pure.pop_back();
-      pure.back() = false;
-    }
-  }
-  return ns;
+// Mask slots the wave-per-chunk kernel (pgx_roaring_program_wave) needs for one program by its own plan walk
+// (pgx_internal.h RPlan, which the kernel steps as well), or -1 for a program that walk cannot take.
+int rprog_wave_slots(const RProg& r) {
+  RPlan plan;
+  for (int i = 0; i < r.nops;) i += plan.step(r, i);
+  return plan.fits() ? plan.ns : -1;
 }
 
-// The wave kernel's own plan walk (pgx_roaring_program_wave) keeps the operand stack as 4-bit entries of one 64-bit
-// word and shifts on every binary op unconditionally: only well-formed programs (each NOT / AND / OR has its operands,
-// one result left), at most 16 operands deep and with slot ids below 8 may take it.  Mirrors the device walk.
-bool rprog_wave_ok(const RProg& r, int* slots) {
-  int depth = 0, maxd = 0, ns = 0;
-  std::vector<bool> pure;
-  for (int i = 0; i < r.nops; ++i) {
-    const int op = r.op[i];
-    if (op == RP_LEAF) {
-      const bool top = !pure.empty() && pure.back();
-      const bool f_or = top && i + 1 < r.nops && r.op[i + 1] == RP_OR;
-      const bool f_andnot = top && !f_or && i + 2 < r.nops && r.op[i + 1] == RP_NOT && r.op[i + 2] == RP_AND;
-      if (f_or) {
-        ++i;
-      } else if (f_andnot) {
-        pure.back() = false;
-        i += 2;
-      } else {
-        pure.push_back(true);
-        ++ns;
-        maxd = std::max(maxd, ++depth);
-      }
-    } else if (op == RP_NOT) {
-      if (depth < 1) return false;
-      pure.back() = false;
-    } else if (op == RP_AND || op == RP_OR) {
-      if (depth < 2) return false;
-      --depth;
-      pure.pop_back();
-      pure.back() = false;
-    } else {
-      return false;
-    }
-  }
-  if (depth != 1 || maxd > 16 || ns > 7) return false;
-  if (slots) *slots = ns;
-  return true;
+// Bitmaps of one program: the wave kernel gives each a lane, the per-segment walk a thread.
+int rprog_bitmaps(const ExecPlan& P, const RProg& r) {
+  int nb = 0;
+  for (int k = 0; k < r.nops; ++k)
+    if (r.op[k] == RP_LEAF && r.arg[k] >= 0) nb += P.roar[r.arg[k]].nb;
+  return nb;
 }
 
 // Bitmap programs [p0, p1) (default: all of them).
@@ -139,13 +85,8 @@ void launch_bitmaps(ExecPlan& P, hipStream_t st, int p0 = 0, int p1 = -1) {
       bool wave = rk == RPROG_AUTO || rk == RPROG_WAVE;
       int nslots = 1;
       for (size_t i = 0; i < P.rprogs.size() && wave; ++i) {
-        const RProg& r = P.rprogs[i];
-        int nb = 0;
-        for (int k = 0; k < r.nops; ++k)
-          if (r.op[k] == RP_LEAF && r.arg[k] >= 0) nb += P.roar[r.arg[k]].nb;
-        int ns = 0;
-        if (!rprog_wave_ok(r, &ns) || ns != rprog_slots(r)) wave = false;
-        if (nb > 64 || ns > 3) wave = false;
+        const int ns = rprog_wave_slots(P.rprogs[i]);
+        if (ns < 0 || ns > 3 || rprog_bitmaps(P, P.rprogs[i]) > 64) wave = false;
         nslots = std::max(nslots, ns);
       }
       int maxleaves = 0;  // leaf masks the wide kernel keeps in LDS (PGX_RPROG=stack: the stack kernel)
@@ -158,13 +99,8 @@ void launch_bitmaps(ExecPlan& P, hipStream_t st, int p0 = 0, int p1 = -1) {
         if (rk == RPROG_STACK) maxleaves = 0;
         // per-segment container walk when every program's bitmaps fit one lane each (PGX_RPROG=chunk: per-chunk kernels)
         bool seg_walk = maxleaves >= 1 && rk != RPROG_CHUNK && rk != RPROG_STACK;
-        for (size_t i = 0; i < P.rprogs.size() && seg_walk; ++i) {
-          int nb = 0;
-          const RProg& r = P.rprogs[i];
-          for (int k = 0; k < r.nops; ++k)
-            if (r.op[k] == RP_LEAF && r.arg[k] >= 0) nb += P.roar[r.arg[k]].nb;
-          if (nb > 512) seg_walk = false;
-        }
+        for (size_t i = 0; i < P.rprogs.size() && seg_walk; ++i)
+          if (rprog_bitmaps(P, P.rprogs[i]) > 512) seg_walk = false;
         if (seg_walk) maxleaves = -maxleaves;
       }
       P.rp_kind = wave ? 0 : 1;

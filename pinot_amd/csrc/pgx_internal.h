@@ -32,7 +32,7 @@ enum LeafMode : int8_t {
   LEAF_RCHUNK = 6,         // query kernels: a bitmap program evaluated per 65536-doc chunk into LDS by the kernel
 };
 
-// Bitmap inverted-index expansion (pgx_kernels.hip pgx_roaring_expand): one descriptor per (segment, leaf).  The
+// Bitmap inverted-index expansion (pgx_roaring.hip pgx_roaring_expand): one descriptor per (segment, leaf).  The
 // layout is shared with the generated query kernels (pgx_jit_abi.h JRDesc), which evaluate bitmap programs per chunk
 // themselves (LEAF_RCHUNK).
 //   mask: nchunks x 2048 words: bit (doc & 31) of word (doc >> 5); inv: device copy of <col>.bitmap.inv;
@@ -44,6 +44,69 @@ using RDesc = ::JRDesc;
 constexpr int kMaxRProg = PGX_J_MAX_RPROG;
 enum RProgOp : int8_t { RP_LEAF = 0, RP_AND = 1, RP_OR = 2, RP_NOT = 3 };
 using RProg = ::JRProg;
+
+// Slot plan of the wave-per-chunk kernel (pgx_roaring_program_wave), the one statement of its rule: the kernel's lane
+// assignment, its evaluation and the host's choice of the kernel (pgx_host.cpp rprog_wave_slots) all step this walker.
+// Leaves share mask "slots" while the slot's operand is still "pure" (an OR of leaves, nothing applied to it yet):
+//   * a leaf directly followed by OR is ORed into the pure top operand's slot (phase 0);
+//   * a leaf directly followed by NOT, AND is cleared out of the pure top operand's slot (phase 1: AND-NOT, after
+//     every phase-0 container of the chunk), which leaves the slot impure;
+//   * every other leaf takes a new slot.
+// C5's (f1 IN .. OR f2 = 7) AND NOT f3 = 3 thus needs ONE 8 KiB slot per wave.  The operand stack is one 64-bit word of
+// 4-bit entries (slot in bits 0-2, "pure" in bit 3, top in bits 0-3) and shifts on every binary op unconditionally, so
+// only programs that pass fits() may be walked on the device.  Everything here is wave-uniform (scalar registers), and
+// what a caller does not read (the device never reads depth, max_depth or ok) is dropped by the compiler.
+#ifdef __HIPCC__
+#define PGX_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define PGX_HD inline
+#endif
+struct RPlan {
+  uint64_t stk = 0;
+  int ns = 0;                    // slots handed out
+  int depth = 0, max_depth = 0;  // operands on the stack
+  bool ok = true;                // every op known and given its operands so far
+  // of the last step(): a leaf's slot and phase; NOT's operand slot; AND / OR's left (= result) slot and right slot rhs
+  int slot = 0, phase = 0, rhs = 0;
+  // Applies op i and returns how many ops that consumed: a fused leaf takes its OR / its NOT, AND with it.
+  PGX_HD int step(const RProg& P, int i) {
+    const int op = P.op[i];
+    if (op == RP_LEAF) {
+      int f = 0;
+      if (stk & 8u) {
+        if (i + 1 < P.nops && P.op[i + 1] == RP_OR) f = 1;
+        else if (i + 2 < P.nops && P.op[i + 1] == RP_NOT && P.op[i + 2] == RP_AND) f = 2;
+      }
+      if (!f) {
+        stk = (stk << 4) | 8u | static_cast<uint64_t>(ns);
+        ++ns;
+        ++depth;
+        max_depth = depth > max_depth ? depth : max_depth;
+      }
+      slot = top();
+      phase = f == 2 ? 1 : 0;
+      if (f == 2) stk &= ~uint64_t(8);
+      return 1 + f;
+    }
+    if (op == RP_NOT) {
+      ok &= depth >= 1;
+      slot = top();
+    } else if (op == RP_AND || op == RP_OR) {
+      ok &= depth >= 2;
+      --depth;
+      rhs = top();
+      stk >>= 4;  // drop the right operand; the left one holds the result
+      slot = top();
+    } else {
+      ok = false;
+    }
+    stk &= ~uint64_t(8);  // no longer pure
+    return 1;
+  }
+  PGX_HD int top() const { return static_cast<int>(stk & 7u); }
+  // after the last op: well formed (one result left), at most 16 operands deep, slot ids below 8
+  PGX_HD bool fits() const { return ok && depth == 1 && max_depth <= 16 && ns <= 7; }
+};
 
 enum ProgOp : int8_t { OP_LEAF = 0, OP_AND = 1, OP_OR = 2, OP_STAT = 3, OP_TRUE = 4 };
 

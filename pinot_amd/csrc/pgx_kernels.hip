@@ -658,805 +658,8 @@ __global__ void __launch_bounds__(256) pgx_compact(const unsigned long long* tab
 }
 
 
-// ---------------------------------------------------------------------------------------------
-// a-7: bitmap inverted-index leaves.  The reference ORs the RoaringBitmap of every matching dictId
-// (operator/filter/BitmapBasedFilterOperator.java:62-92, segment/index/readers/BitmapInvertedIndexReader.java:91-117;
-// RoaringBitmap 0.5.10 portable format without run containers: cookie 12346, container count, (key, card-1) u16
-// pairs, u32 offsets, then array (<= 4096 u16) or bitmap (1024 u64) containers).  One workgroup expands one
-// 65536-doc chunk of one (segment, leaf): each lane binary-searches one bitmap's container keys for the chunk, then
-// the workgroup ORs the found containers into an 8 KiB LDS mask (array containers bit by bit with LDS atomics, bitmap
-// containers word by word) and writes the 2048 mask words to HBM with coalesced stores.  Roaring bytes are only
-// 2-byte aligned inside the inverted-index file, so multi-byte fields are read as u16 pairs.
-// ---------------------------------------------------------------------------------------------
+// Global address space (the bitmap kernels, pgx_roaring.hip, define their own).
 #define PGX_GLOBAL __attribute__((address_space(1)))
-// Global-address-space loads: flat loads would share the LDS counter with the mask atomics and serialise them.
-__device__ __forceinline__ uint32_t rd16(const uint8_t* p) { return *(const PGX_GLOBAL uint16_t*)(p); }
-__device__ __forceinline__ uint32_t rd32(const uint8_t* p) { return rd16(p) | (rd16(p + 2) << 16); }
-// Bitmap k of a descriptor: its dictId's entry of the .bitmap.inv header (BE int offsets, 4-byte aligned) locates it.
-__device__ __forceinline__ const uint8_t* rbitmap(const RDesc& D, int k) {
-  const uint32_t id = D.ids[k];
-  return D.inv + __builtin_bswap32(((const PGX_GLOBAL uint32_t*)(D.inv))[id]);
-}
-
-constexpr int kRoarBatch = 256;
-
-// ORs the containers of D's bitmaps for one chunk into the LDS mask m (2048 words, zeroed by the caller).  Every
-// thread of the 256-lane workgroup must call it (it synchronises).
-__device__ void roar_or_chunk(const RDesc& D, int chunk, uint32_t* m, const uint8_t** cptr, int* ccard, int* cpre,
-                              int* ncont, int* celems) {
-  const int tid = threadIdx.x;
-  for (int b0 = 0; b0 < D.nb; b0 += kRoarBatch) {
-    if (tid == 0) *ncont = 0;
-    __syncthreads();
-    const int b = b0 + tid;
-    if (b < D.nb) {
-      const uint8_t* base = rbitmap(D, b);
-      const int n = static_cast<int>(rd32(base + 4));
-      // keys are sorted and distinct, so a bitmap with a container in every chunk holds chunk c at index c: probe
-      // there first (one load for dense bitmaps), then binary-search the rest of the range
-      int lo = 0, hi = n - 1, found = -1;
-      const int g = min(chunk, n - 1);
-      if (g >= 0) {
-        const uint32_t kv = rd32(base + 8 + 4 * g);  // key | (card - 1) << 16
-        const int k = static_cast<int>(kv & 0xFFFFu);
-        if (k == chunk) found = g;
-        else if (k < chunk) lo = g + 1;
-        else hi = g - 1;
-      }
-      while (found < 0 && lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        const int k = static_cast<int>(rd16(base + 8 + 4 * mid));
-        if (k == chunk) { found = mid; break; }
-        if (k < chunk) lo = mid + 1; else hi = mid - 1;
-      }
-      if (found >= 0) {
-        const int card = static_cast<int>(rd16(base + 8 + 4 * found + 2)) + 1;
-        const uint32_t off = rd32(base + 8 + 4 * n + 4 * found);
-        const int slot = atomicAdd(ncont, 1);
-        cptr[slot] = base + off;
-        ccard[slot] = card;
-      }
-    }
-    __syncthreads();
-    const int nc = *ncont;
-    // array containers: exclusive prefix of their cardinalities (wave 0, 4 entries per lane), then every lane takes
-    // elements of any container with 4 loads in flight before the LDS atomics (a loop over containers would chain one
-    // global-load latency per container)
-    if (tid < 64) {
-      int v[4], x = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = tid * 4 + j;
-        v[j] = (k < nc && ccard[k] <= 4096) ? ccard[k] : 0;
-        x += v[j];
-      }
-      int incl = x;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(incl, d, 64);
-        if (tid >= d) incl += y;
-      }
-      int e = incl - x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cpre[tid * 4 + j] = e;
-        e += v[j];
-      }
-      if (tid == 63) *celems = incl;
-    }
-    __syncthreads();
-    const int ne = *celems;
-    for (int e0 = 0; e0 < ne; e0 += 4 * 256) {
-      uint32_t val[4];
-      bool ok[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = e0 + j * 256 + tid;
-        ok[j] = e < ne;
-        if (ok[j]) {
-          int lo = 0, hi = nc - 1;  // the last container with cpre <= e holds element e (empty parts repeat cpre)
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (cpre[mid] <= e) lo = mid; else hi = mid - 1;
-          }
-          val[j] = rd16(cptr[lo] + 2 * (e - cpre[lo]));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (ok[j]) atomicOr(&m[val[j] >> 5], 1u << (val[j] & 31u));
-    }
-    for (int k = 0; k < nc; ++k) {  // bitmap containers: 1024 x u64 LE == 2048 x u32, bit j of word w = doc 32w + j
-      if (ccard[k] <= 4096) continue;
-      const uint8_t* c = cptr[k];
-      for (int w = tid; w < 2048; w += 256) {
-        const uint32_t x = rd32(c + 4 * w);
-        if (x) atomicOr(&m[w], x);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(256) pgx_roaring_expand(const RDesc* __restrict__ descs, int npairs, int maxchunks) {
-  const int pair = static_cast<int>(blockIdx.x / maxchunks);
-  const int chunk = static_cast<int>(blockIdx.x - static_cast<unsigned>(pair) * maxchunks);
-  if (pair >= npairs) return;
-  const RDesc D = descs[pair];
-  if (chunk >= D.nchunks) return;
-  __shared__ uint32_t m[2048];
-  __shared__ const uint8_t* cptr[kRoarBatch];
-  __shared__ int ccard[kRoarBatch], cpre[kRoarBatch];
-  __shared__ int ncont, celems;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < 2048; i += 256) m[i] = 0u;
-  roar_or_chunk(D, chunk, m, cptr, ccard, cpre, &ncont, &celems);
-  uint32_t* out = D.mask + static_cast<size_t>(chunk) * 2048;
-  for (int i = tid; i < 2048; i += 256) out[i] = m[i];
-}
-
-// AND / OR / NOT over bitmap leaves for one 65536-doc chunk (AndBlockDocIdSet.fastIterator's bitmap AND,
-// OrBlockDocIdSet's bitmap OR, BitmapDocIdSet's exclusion flip): a stack of LDS masks, each leaf expanded with
-// roar_or_chunk, the result written once.  One workgroup per (program, chunk).
-constexpr int kRProgStack = 4;
-__global__ void __launch_bounds__(256) pgx_roaring_program(const RProg* __restrict__ progs, const RDesc* __restrict__ descs,
-                                                           int nprogs, int maxchunks) {
-  const int pi = static_cast<int>(blockIdx.x / maxchunks);
-  const int chunk = static_cast<int>(blockIdx.x - static_cast<unsigned>(pi) * maxchunks);
-  if (pi >= nprogs) return;
-  const RProg& P = progs[pi];
-  if (chunk >= P.nchunks) return;
-  __shared__ uint32_t stk[kRProgStack][2048];
-  __shared__ const uint8_t* cptr[kRoarBatch];
-  __shared__ int ccard[kRoarBatch], cpre[kRoarBatch];
-  __shared__ int ncont, celems;
-  const int tid = threadIdx.x;
-  const int64_t doc0 = static_cast<int64_t>(chunk) << 16;
-  int sp = 0;
-  for (int i = 0; i < P.nops; ++i) {
-    const int op = P.op[i];
-    if (op == RP_LEAF) {
-      uint32_t* m = stk[sp];
-      for (int w = tid; w < 2048; w += 256) m[w] = 0u;
-      __syncthreads();
-      const int a = P.arg[i];
-      if (a >= 0) roar_or_chunk(descs[a], chunk, m, cptr, ccard, cpre, &ncont, &celems);
-      ++sp;
-    } else if (op == RP_NOT) {
-      uint32_t* m = stk[sp - 1];
-      for (int w = tid; w < 2048; w += 256) {
-        const int64_t d = doc0 + 32 * w;  // first doc of the word
-        uint32_t keep = 0xFFFFFFFFu;       // bits inside [0, num_docs)
-        if (d >= P.num_docs) keep = 0u;
-        else if (d + 32 > P.num_docs) keep = (1u << (P.num_docs - d)) - 1u;
-        m[w] = ~m[w] & keep;
-      }
-    } else {
-      uint32_t* a = stk[sp - 2];
-      const uint32_t* b = stk[sp - 1];
-      for (int w = tid; w < 2048; w += 256) a[w] = op == RP_AND ? (a[w] & b[w]) : (a[w] | b[w]);
-      --sp;
-    }
-    __syncthreads();
-  }
-  uint32_t* out = P.mask + static_cast<size_t>(chunk) * 2048;
-  for (int w = tid; w < 2048; w += 256) out[w] = stk[0][w];
-}
-
-// The same program with every leaf expanded at once: one container search over ALL bitmaps of ALL leaves (a lane per
-// bitmap), one pass over all their array-container elements (4 loads in flight per lane, LDS atomics into the leaf's
-// own mask), the bitmap containers, then the AND / OR / NOT program evaluated per mask word in registers and written
-// straight out.  The dependent global-load chain is that of ONE leaf, not one per leaf (C5: 3 leaves, 34 bitmaps), and
-// the LDS holds exactly the program's leaf masks (dynamic LDS, nleaves x 8 KiB).
-constexpr int kRProgMaxLeaves = 8;
-__global__ void __launch_bounds__(256) pgx_roaring_program_wide(const RProg* __restrict__ progs,
-                                                                const RDesc* __restrict__ descs, int nprogs,
-                                                                int maxchunks) {
-  const int pi = static_cast<int>(blockIdx.x / maxchunks);
-  const int chunk = static_cast<int>(blockIdx.x - static_cast<unsigned>(pi) * maxchunks);
-  if (pi >= nprogs) return;
-  const RProg& P = progs[pi];
-  if (chunk >= P.nchunks) return;
-  extern __shared__ uint32_t lmask[];  // [leaf][2048]
-  __shared__ const uint8_t* cptr[kRoarBatch];
-  __shared__ int ccard[kRoarBatch], cpre[kRoarBatch], cleaf[kRoarBatch];
-  __shared__ int ncont, celems;
-  __shared__ int leaf_desc[kRProgMaxLeaves], leaf_b0[kRProgMaxLeaves + 1];
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    int nl = 0, tot = 0;
-    for (int i = 0; i < P.nops; ++i)
-      if (P.op[i] == RP_LEAF) {
-        const int a = P.arg[i];
-        leaf_desc[nl] = a;
-        leaf_b0[nl] = tot;
-        tot += a >= 0 ? descs[a].nb : 0;
-        ++nl;
-      }
-    leaf_b0[nl] = tot;
-    ncont = nl;  // leaves, read below before the first batch reuses ncont
-  }
-  __syncthreads();
-  const int nl = ncont;
-  const int total_b = leaf_b0[nl];
-  for (int i = tid; i < nl * 2048; i += 256) lmask[i] = 0u;
-  for (int b0 = 0; b0 < total_b; b0 += kRoarBatch) {
-    __syncthreads();
-    if (tid == 0) ncont = 0;
-    __syncthreads();
-    const int b = b0 + tid;
-    if (b < total_b) {
-      int j = 0;
-      while (leaf_b0[j + 1] <= b) ++j;  // the leaf this bitmap belongs to (<= 8 leaves)
-      const RDesc& D = descs[leaf_desc[j]];
-      const uint8_t* base = rbitmap(D, b - leaf_b0[j]);
-      const int n = static_cast<int>(rd32(base + 4));
-      int lo = 0, hi = n - 1, found = -1;
-      const int g = min(chunk, n - 1);
-      if (g >= 0) {
-        const uint32_t kv = rd32(base + 8 + 4 * g);
-        const int k = static_cast<int>(kv & 0xFFFFu);
-        if (k == chunk) found = g;
-        else if (k < chunk) lo = g + 1;
-        else hi = g - 1;
-      }
-      while (found < 0 && lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        const int k = static_cast<int>(rd16(base + 8 + 4 * mid));
-        if (k == chunk) { found = mid; break; }
-        if (k < chunk) lo = mid + 1; else hi = mid - 1;
-      }
-      if (found >= 0) {
-        const int card = static_cast<int>(rd16(base + 8 + 4 * found + 2)) + 1;
-        const uint32_t off = rd32(base + 8 + 4 * n + 4 * found);
-        const int slot = atomicAdd(&ncont, 1);
-        cptr[slot] = base + off;
-        ccard[slot] = card;
-        cleaf[slot] = j;
-      }
-    }
-    __syncthreads();
-    const int nc = ncont;
-    if (tid < 64) {
-      int v[4], x = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int k = tid * 4 + q;
-        v[q] = (k < nc && ccard[k] <= 4096) ? ccard[k] : 0;
-        x += v[q];
-      }
-      int incl = x;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(incl, d, 64);
-        if (tid >= d) incl += y;
-      }
-      int e = incl - x;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        cpre[tid * 4 + q] = e;
-        e += v[q];
-      }
-      if (tid == 63) celems = incl;
-    }
-    __syncthreads();
-    const int ne = celems;
-    for (int e0 = 0; e0 < ne; e0 += 4 * 256) {
-      uint32_t val[4];
-      int dst[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int e = e0 + q * 256 + tid;
-        dst[q] = -1;
-        if (e < ne) {
-          int lo = 0, hi = nc - 1;
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (cpre[mid] <= e) lo = mid; else hi = mid - 1;
-          }
-          val[q] = rd16(cptr[lo] + 2 * (e - cpre[lo]));
-          dst[q] = cleaf[lo] * 2048;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (dst[q] >= 0) atomicOr(&lmask[dst[q] + (val[q] >> 5)], 1u << (val[q] & 31u));
-    }
-    for (int k = 0; k < nc; ++k) {
-      if (ccard[k] <= 4096) continue;
-      const uint8_t* c = cptr[k];
-      uint32_t* m = lmask + cleaf[k] * 2048;
-      for (int w = tid; w < 2048; w += 256) {
-        const uint32_t x = rd32(c + 4 * w);
-        if (x) atomicOr(&m[w], x);
-      }
-    }
-  }
-  __syncthreads();
-  // the program, per mask word, in registers
-  const int64_t doc0 = static_cast<int64_t>(chunk) << 16;
-  uint32_t* out = P.mask + static_cast<size_t>(chunk) * 2048;
-  for (int w = tid; w < 2048; w += 256) {
-    uint32_t st[kRProgStack + 4];
-    int sp = 0, leaf = 0;
-    const int64_t d = doc0 + 32 * w;
-    const uint32_t keep = d >= P.num_docs ? 0u : (d + 32 > P.num_docs ? (1u << (P.num_docs - d)) - 1u : 0xFFFFFFFFu);
-    for (int i = 0; i < P.nops; ++i) {
-      const int op = P.op[i];
-      if (op == RP_LEAF) {
-        st[sp++] = lmask[leaf * 2048 + w];
-        ++leaf;
-      } else if (op == RP_NOT) {
-        st[sp - 1] = ~st[sp - 1] & keep;
-      } else {
-        st[sp - 2] = op == RP_AND ? (st[sp - 2] & st[sp - 1]) : (st[sp - 2] | st[sp - 1]);
-        --sp;
-      }
-    }
-    out[w] = st[0];
-  }
-}
-
-// One workgroup per (segment, program), walking the segment's 65536-doc chunks in order.  Every bitmap of the program
-// (<= kSegRBitmaps, one lane each) keeps a cursor into its sorted container keys, and the key / cardinality / offset of
-// its NEXT container are loaded while the current chunk is expanded, so a chunk costs the element and bitmap-word loads
-// only (the per-chunk kernels above pay a container search of four dependent loads per chunk).  Array elements spread
-// over all lanes (4 loads in flight each), bitmap-container words too; the AND / OR / NOT program is evaluated per mask
-// word in registers and the chunk's mask written out.
-constexpr int kSegRThreads = 512;
-constexpr int kSegRBitmaps = 512;
-// Workgroup barrier that orders LDS only: no s_waitcnt vmcnt(0), so global loads issued before it (next container's
-// fields) and the mask stores of the previous chunk are not drained at every phase of the chunk loop.  Global memory
-// is never communicated between the workgroup's threads here.
-__device__ __forceinline__ void seg_lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-__global__ void __launch_bounds__(kSegRThreads, 8) pgx_roaring_program_seg(const RProg* __restrict__ progs,
-                                                                        const RDesc* __restrict__ descs, int nprogs,
-                                                                        int parts) {
-  // `parts` workgroups per segment, each walking a contiguous range of its chunks: short segment lists (a batch of a
-  // long query) still put enough workgroups on the chip
-  const int pi = static_cast<int>(blockIdx.x) / parts;
-  if (pi >= nprogs) return;
-  const RProg& P = progs[pi];
-  const int per = (P.nchunks + parts - 1) / parts;
-  const int c0 = (static_cast<int>(blockIdx.x) % parts) * per;
-  const int c1 = min(P.nchunks, c0 + per);
-  if (c0 >= c1) return;
-  extern __shared__ uint32_t lmask[];  // [leaf][2048]
-  __shared__ const uint8_t* cptr[kSegRBitmaps];
-  __shared__ int ccard[kSegRBitmaps], cpre[kSegRBitmaps + 1], cleaf[kSegRBitmaps];
-  __shared__ int ncont;
-  const int tid = threadIdx.x;
-  // leaves in program order (uniform loads); lane tid < total bitmaps owns bitmap (tid - first) of leaf `leaf`
-  int nl = 0, tot = 0, leaf = 0, my_desc = -1, my_first = 0;
-  for (int i = 0; i < P.nops; ++i)
-    if (P.op[i] == RP_LEAF && nl < kRProgMaxLeaves) {
-      const int a = P.arg[i];
-      const int nb = a >= 0 ? descs[a].nb : 0;
-      if (tid >= tot && tid < tot + nb) {
-        leaf = nl;
-        my_desc = a;
-        my_first = tot;
-      }
-      tot += nb;
-      ++nl;
-    }
-  // this lane's bitmap: header, container count and the fields of its first container (the host launches this
-  // kernel only when the program's bitmaps number <= kSegRBitmaps)
-  const uint8_t* base = nullptr;
-  int n = 0, cur = 0, key = 1 << 30, card = 0;
-  uint32_t off = 0;
-  if (my_desc >= 0) {
-    const RDesc& D = descs[my_desc];
-    base = rbitmap(D, tid - my_first);
-    n = static_cast<int>(rd32(base + 4));
-    if (c0 > 0 && n > 0) {  // first container with key >= c0: keys are strictly increasing, so key[c0] == c0 settles it
-      if (n > c0 && static_cast<int>(rd16(base + 8 + 4 * c0)) == c0) {
-        cur = c0;
-      } else {
-        int lo = 0, hi = n;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (static_cast<int>(rd16(base + 8 + 4 * mid)) < c0) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
-      }
-    }
-    if (cur < n) {
-      key = static_cast<int>(rd16(base + 8 + 4 * cur));
-      card = static_cast<int>(rd16(base + 8 + 4 * cur + 2)) + 1;
-      off = rd32(base + 8 + 4 * n + 4 * cur);
-    }
-  }
-  __shared__ int bidx[kSegRBitmaps], nbm;
-  constexpr int kPer = 4;  // array elements in flight per lane (8 costs a quarter of the workgroups per CU)
-  for (int chunk = c0; chunk < c1; ++chunk) {
-    for (int i = tid; i < nl * 2048; i += kSegRThreads) lmask[i] = 0u;
-    if (tid == 0) ncont = 0;
-    // LDS-only barriers: the container-field prefetches and the previous chunk's mask stores stay in flight
-    seg_lds_barrier();
-    if (key == chunk) {
-      const int slot = atomicAdd(&ncont, 1);
-      cptr[slot] = base + off;
-      ccard[slot] = card;
-      cleaf[slot] = leaf;
-      // advance the cursor and prefetch the next container's fields (consumed at a later chunk)
-      ++cur;
-      if (cur < n) {
-        key = static_cast<int>(rd16(base + 8 + 4 * cur));
-        card = static_cast<int>(rd16(base + 8 + 4 * cur + 2)) + 1;
-        off = rd32(base + 8 + 4 * n + 4 * cur);
-      } else {
-        key = 1 << 30;
-      }
-    }
-    seg_lds_barrier();
-    const int nc = ncont;
-    if (tid < 64) {  // exclusive prefix of the array containers' cardinalities (8 per lane); bitmap containers listed
-      int v[8], x = 0, nb = 0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int k = tid * 8 + q;
-        const bool in = k < nc;
-        v[q] = (in && ccard[k] <= 4096) ? ccard[k] : 0;
-        nb += (in && ccard[k] > 4096) ? 1 : 0;
-        x += v[q];
-      }
-      int incl = x, binc = nb;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(incl, d, 64);
-        const int z = __shfl_up(binc, d, 64);
-        if (tid >= d) {
-          incl += y;
-          binc += z;
-        }
-      }
-      int e = incl - x, b = binc - nb;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int k = tid * 8 + q;
-        if (k < kSegRBitmaps) cpre[k] = e;
-        e += v[q];
-        if (k < nc && ccard[k] > 4096) bidx[b++] = k;
-      }
-      if (tid == 63) {
-        cpre[kSegRBitmaps] = incl;
-        nbm = binc;
-      }
-    }
-    seg_lds_barrier();
-    const int ne = cpre[kSegRBitmaps];
-    const int nbc = nbm;
-    // the first bitmap container's words are requested before the array elements, so both round trips overlap
-    constexpr int kWords = 2048 / kSegRThreads;
-    uint32_t bw[kWords];
-    if (nbc > 0) {
-      const uint8_t* c = cptr[bidx[0]];
-#pragma unroll
-      for (int q = 0; q < kWords; ++q) bw[q] = rd32(c + 4 * (q * kSegRThreads + tid));
-    }
-    for (int e0 = 0; e0 < ne; e0 += kPer * kSegRThreads) {
-      uint32_t val[kPer];
-      int dst[kPer];
-#pragma unroll
-      for (int q = 0; q < kPer; ++q) {
-        const int e = e0 + q * kSegRThreads + tid;
-        dst[q] = -1;
-        if (e < ne) {
-          int lo = 0, hi = nc - 1;
-          while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (cpre[mid] <= e) lo = mid; else hi = mid - 1;
-          }
-          val[q] = rd16(cptr[lo] + 2 * (e - cpre[lo]));
-          dst[q] = cleaf[lo] * 2048;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < kPer; ++q)
-        if (dst[q] >= 0) atomicOr(&lmask[dst[q] + (val[q] >> 5)], 1u << (val[q] & 31u));
-    }
-    for (int i = 0; i < nbc; ++i) {  // bitmap containers: all words in flight, then the ORs
-      const int k = bidx[i];
-      if (i > 0) {
-        const uint8_t* c = cptr[k];
-#pragma unroll
-        for (int q = 0; q < kWords; ++q) bw[q] = rd32(c + 4 * (q * kSegRThreads + tid));
-      }
-      uint32_t* m = lmask + cleaf[k] * 2048;
-#pragma unroll
-      for (int q = 0; q < kWords; ++q)
-        if (bw[q]) atomicOr(&m[q * kSegRThreads + tid], bw[q]);
-    }
-    seg_lds_barrier();
-    const int64_t doc0 = static_cast<int64_t>(chunk) << 16;
-    uint32_t* out = P.mask + static_cast<size_t>(chunk) * 2048;
-    for (int w = tid; w < 2048; w += kSegRThreads) {
-      uint32_t st[kRProgStack + 4];
-      int sp = 0, lf = 0;
-      const int64_t d = doc0 + 32 * w;
-      const uint32_t keep = d >= P.num_docs ? 0u : (d + 32 > P.num_docs ? (1u << (P.num_docs - d)) - 1u : 0xFFFFFFFFu);
-      for (int i = 0; i < P.nops; ++i) {
-        const int op = P.op[i];
-        if (op == RP_LEAF) {
-          st[sp++] = lmask[lf * 2048 + w];
-          ++lf;
-        } else if (op == RP_NOT) {
-          st[sp - 1] = ~st[sp - 1] & keep;
-        } else {
-          st[sp - 2] = op == RP_AND ? (st[sp - 2] & st[sp - 1]) : (st[sp - 2] | st[sp - 1]);
-          --sp;
-        }
-      }
-      out[w] = st[0];
-    }
-    seg_lds_barrier();  // lmask is zeroed for the next chunk
-  }
-}
-
-// Wave-per-chunk form of the bitmap programs: every wavefront walks its own range of one segment's chunks with its own
-// LDS masks, and the workgroup never synchronises (the workgroup kernel above spends most of a chunk waiting at five
-// barriers for its slowest wave).  Lane b owns bitmap b of the program (<= 64 bitmaps) and its container cursor.
-// Leaves share mask "slots" while the slot's operand is still "pure" (an OR of leaves, nothing applied to it yet):
-//   * a leaf directly followed by OR is ORed into the pure top operand's slot (phase 0);
-//   * a leaf directly followed by NOT, AND is cleared out of the pure top operand's slot (phase 1: AND-NOT, after
-//     every phase-0 container of the chunk), which leaves the slot impure.
-// C5's (f1 IN .. OR f2 = 7) AND NOT f3 = 3 thus needs ONE 8 KiB slot per wave.  The rest of the postfix program is
-// evaluated over the slots and the chunk's mask written.  The plan is a walk of the program with a 4-bit-per-entry
-// stack in one 64-bit word (slot in bits 0-2, "pure" in bit 3); the host applies the same rule (rprog_slots).
-#ifndef PGX_WAVE_ELEMS
-#define PGX_WAVE_ELEMS 16  // array elements per lane in flight (C5: 16 -> 0.75 ms, 8 -> 0.79, 32 with per-element searches slower)
-#endif
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Fusion of the leaf at op i into the top operand: 0 none, 1 OR (skips op i + 1), 2 AND-NOT (skips ops i + 1, i + 2).
-__device__ __forceinline__ int rprog_fusion(const RProg& P, int i, uint64_t stk) {
-  if (!(stk & 8u)) return 0;
-  if (i + 1 < P.nops && P.op[i + 1] == RP_OR) return 1;
-  if (i + 2 < P.nops && P.op[i + 1] == RP_NOT && P.op[i + 2] == RP_AND) return 2;
-  return 0;
-}
-
-template <int NS, int WPB, int MINW>
-__global__ void __launch_bounds__(64 * WPB, MINW) pgx_roaring_program_wave(const RProg* __restrict__ progs,
-                                                                          const RDesc* __restrict__ descs, int nprogs,
-                                                                          int parts) {
-  extern __shared__ uint32_t wmask[];  // [wave][NS][2048]
-  __shared__ int wpre[WPB][65];
-  __shared__ const uint8_t* wptr[WPB][64];
-  __shared__ int wslot[WPB][64];
-  const int lane = static_cast<int>(threadIdx.x) & 63, wv = static_cast<int>(threadIdx.x) >> 6;
-  const int gw = static_cast<int>(blockIdx.x) * WPB + wv;
-  const int pi = gw / parts;
-  if (pi >= nprogs) return;  // per wave: nothing below synchronises the workgroup
-  const RProg& P = progs[pi];
-  const int per = (P.nchunks + parts - 1) / parts;
-  const int c0 = (gw % parts) * per;
-  const int c1 = min(P.nchunks, c0 + per);
-  if (c0 >= c1) return;
-  uint32_t* sm = wmask + wv * NS * 2048;
-  int* pre = wpre[wv];
-  const uint8_t** ptrs = wptr[wv];
-  int* slots = wslot[wv];
-  // slot plan: this lane's bitmap, its leaf's slot and phase
-  int my_desc = -1, my_first = 0, my_slot = 0, my_phase = 0;
-  bool any_andnot = false;
-  {
-    uint64_t stk = 0;
-    int ns = 0, tot = 0;
-    for (int i = 0; i < P.nops; ++i) {
-      const int op = P.op[i];
-      if (op == RP_LEAF) {
-        const int a = P.arg[i];
-        const int nb = a >= 0 ? descs[a].nb : 0;
-        const int f = rprog_fusion(P, i, stk);
-        const int slot = f ? static_cast<int>(stk & 7u) : ns;
-        if (!f) {
-          stk = (stk << 4) | 8u | static_cast<uint64_t>(ns);
-          ++ns;
-        }
-        if (lane >= tot && lane < tot + nb) {
-          my_desc = a;
-          my_first = tot;
-          my_slot = slot;
-          my_phase = f == 2 ? 1 : 0;
-        }
-        tot += nb;
-        if (f == 2) {
-          stk &= ~uint64_t(8);
-          any_andnot = true;
-        }
-        i += f;  // the fused OR / NOT, AND are done by the expansion itself
-      } else if (op == RP_NOT) {
-        stk &= ~uint64_t(8);
-      } else {
-        stk >>= 4;  // drop the right operand; the left one holds the result, no longer pure
-        stk &= ~uint64_t(8);
-      }
-    }
-  }
-  const uint8_t* base = nullptr;
-  int n = 0, cur = 0, key = 1 << 30, card = 0;
-  uint32_t off = 0;
-  if (my_desc >= 0) {
-    const RDesc& D = descs[my_desc];
-    base = rbitmap(D, lane - my_first);
-    n = static_cast<int>(rd32(base + 4));
-    if (c0 > 0 && n > 0) {
-      if (n > c0 && static_cast<int>(rd16(base + 8 + 4 * c0)) == c0) {
-        cur = c0;
-      } else {
-        int lo = 0, hi = n;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (static_cast<int>(rd16(base + 8 + 4 * mid)) < c0) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
-      }
-    }
-    if (cur < n) {
-      key = static_cast<int>(rd16(base + 8 + 4 * cur));
-      card = static_cast<int>(rd16(base + 8 + 4 * cur + 2)) + 1;
-      off = rd32(base + 8 + 4 * n + 4 * cur);
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-    for (int j = 0; j < 32; ++j) sm[s * 2048 + j * 64 + lane] = 0u;
-  for (int chunk = c0; chunk < c1; ++chunk) {
-    const bool act = key == chunk;
-    const uint8_t* cptr = base + off;
-    const int ccard = card;
-    if (act) {  // advance the cursor now; the next container's fields are consumed at a later chunk
-      ++cur;
-      if (cur < n) {
-        key = static_cast<int>(rd16(base + 8 + 4 * cur));
-        card = static_cast<int>(rd16(base + 8 + 4 * cur + 2)) + 1;
-        off = rd32(base + 8 + 4 * n + 4 * cur);
-      } else {
-        key = 1 << 30;
-      }
-    }
-    for (int ph = 0; ph < (any_andnot ? 2 : 1); ++ph) {
-      const bool mine = act && my_phase == ph;
-      const bool arr = mine && ccard <= 4096;
-      const int v = arr ? ccard : 0;
-      int incl = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-      }
-      const int total = __shfl(incl, 63, 64);
-      pre[lane] = incl - v;
-      if (lane == 63) pre[64] = incl;
-      ptrs[lane] = mine ? cptr : nullptr;
-      slots[lane] = my_slot;
-      uint64_t bm = __ballot(mine && ccard > 4096);
-      wave_lds_sync();
-      // array containers: element e of the chunk's concatenated containers, container k with pre[k] <= e < pre[k + 1];
-      // the lane's first element by one search, later ones (64 apart) by stepping forward (about one step each)
-      if (total > 0) {
-        int k = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1)
-          if (pre[k + step] <= lane) k += step;  // largest k <= 63 with pre[k] <= lane
-        int kend = pre[k + 1], kbeg = pre[k];
-        const uint8_t* kp = ptrs[k];
-        int ks = slots[k];
-        constexpr int B = PGX_WAVE_ELEMS;
-        for (int e0 = lane; e0 < total; e0 += 64 * B) {
-          uint32_t val[B];
-          int dst[B];
-#pragma unroll
-          for (int q = 0; q < B; ++q) {
-            const int e = e0 + 64 * q;
-            dst[q] = -1;
-            if (e < total) {
-              while (kend <= e) {
-                ++k;
-                kbeg = kend;
-                kend = pre[k + 1];
-                kp = ptrs[k];
-                ks = slots[k];
-              }
-              val[q] = rd16(kp + 2 * (e - kbeg));
-              dst[q] = ks * 2048;
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < B; ++q)
-            if (dst[q] >= 0) {
-              if (ph == 0) atomicOr(&sm[dst[q] + (val[q] >> 5)], 1u << (val[q] & 31u));
-              else atomicAnd(&sm[dst[q] + (val[q] >> 5)], ~(1u << (val[q] & 31u)));
-            }
-        }
-      }
-      // bitmap containers: 16 words per lane in flight at a time, ORed into (or cleared out of) the leaf's slot
-      while (bm) {
-        const int src = __builtin_ctzll(bm);
-        bm &= bm - 1;
-        const uint8_t* c = ptrs[src];
-        uint32_t* m = sm + slots[src] * 2048;
-        const bool al = (reinterpret_cast<uintptr_t>(c) & 3u) == 0;
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-          uint32_t x[16];
-          if (al) {
-            const PGX_GLOBAL uint32_t* c32 = (const PGX_GLOBAL uint32_t*)(c);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = c32[(h * 16 + j) * 64 + lane];
-          } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x[j] = rd32(c + 4 * ((h * 16 + j) * 64 + lane));
-          }
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            if (x[j]) {
-              if (ph == 0) atomicOr(&m[(h * 16 + j) * 64 + lane], x[j]);
-              else atomicAnd(&m[(h * 16 + j) * 64 + lane], ~x[j]);
-            }
-        }
-      }
-      wave_lds_sync();
-    }
-    // the rest of the program over the slots (same walk as the plan), word j * 64 + lane; result written, slots cleared
-    const int64_t doc0 = static_cast<int64_t>(chunk) << 16;
-    uint32_t* out = P.mask + static_cast<size_t>(chunk) * 2048;
-    uint64_t stk = 0;
-    int ns = 0;
-    for (int i = 0; i < P.nops; ++i) {
-      const int op = P.op[i];
-      if (op == RP_LEAF) {
-        const int f = rprog_fusion(P, i, stk);
-        if (!f) {
-          stk = (stk << 4) | 8u | static_cast<uint64_t>(ns);
-          ++ns;
-        }
-        if (f == 2) stk &= ~uint64_t(8);
-        i += f;
-      } else if (op == RP_NOT) {
-        uint32_t* a = sm + static_cast<int>(stk & 7u) * 2048;
-#pragma unroll 4
-        for (int j = 0; j < 32; ++j) {
-          const int w = j * 64 + lane;
-          const int64_t d = doc0 + 32 * w;
-          const uint32_t keep =
-              d >= P.num_docs ? 0u : (d + 32 > P.num_docs ? (1u << (P.num_docs - d)) - 1u : 0xFFFFFFFFu);
-          a[w] = ~a[w] & keep;
-        }
-        stk &= ~uint64_t(8);
-      } else {
-        const uint32_t* b = sm + static_cast<int>(stk & 7u) * 2048;
-        stk >>= 4;
-        uint32_t* a = sm + static_cast<int>(stk & 7u) * 2048;
-        if (op == RP_AND) {
-#pragma unroll 8
-          for (int j = 0; j < 32; ++j) a[j * 64 + lane] &= b[j * 64 + lane];
-        } else {
-#pragma unroll 8
-          for (int j = 0; j < 32; ++j) a[j * 64 + lane] |= b[j * 64 + lane];
-        }
-        stk &= ~uint64_t(8);
-      }
-    }
-    const uint32_t* r = sm + static_cast<int>(stk & 7u) * 2048;
-#pragma unroll 8
-    for (int j = 0; j < 32; ++j) out[j * 64 + lane] = r[j * 64 + lane];
-    for (int s = 0; s < NS; ++s)
-#pragma unroll 8
-      for (int j = 0; j < 32; ++j) sm[s * 2048 + j * 64 + lane] = 0u;
-    wave_lds_sync();
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Multi-value columns.  One thread owns 32 consecutive docs (one mask word); their values are consecutive in the raw
@@ -2372,15 +1575,6 @@ extern "C" hipError_t pgx_launch_pack_remap(uint32_t* out_words, const int32_t* 
   return hipGetLastError();
 }
 
-extern "C" hipError_t pgx_launch_roaring(const pgx::RDesc* descs, int npairs, int maxchunks, hipStream_t stream) {
-  if (npairs <= 0 || maxchunks <= 0) return hipSuccess;
-  const long long blocks = static_cast<long long>(npairs) * maxchunks;
-  if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pgx::pgx_roaring_expand, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, descs, npairs,
-                     maxchunks);
-  return hipGetLastError();
-}
-
 extern "C" hipError_t pgx_launch_partition(const uint64_t* in, const int64_t* in_off, const unsigned long long* in_cnt,
                                            int in_cstride, int nreg, int reg_div, int64_t in_cap, int chunks_per_reg,
                                            uint64_t keymask, int shift, int nbits, uint64_t* out, int64_t cap,
@@ -2460,47 +1654,6 @@ extern "C" hipError_t pgx_launch_fsm(const pgx::FsmSeg* segs, int nsegs, const u
   if (nsegs > 0)
     hipLaunchKernelGGL(pgx::pgx_fsm_compose, dim3(nsegs), dim3(256), 0, stream, segs, S, T, cnt, stv, pcount, pstate,
                        stats);
-  return hipGetLastError();
-}
-
-// Wave-per-chunk bitmap programs (host: every program <= 64 bitmaps and <= 3 slots).
-extern "C" hipError_t pgx_launch_roaring_program_wave(const pgx::RProg* progs, const pgx::RDesc* descs, int nprogs,
-                                                      int maxchunks, int nslots, hipStream_t stream) {
-  if (nprogs <= 0 || maxchunks <= 0) return hipSuccess;
-  // ~8192 waves (four rounds of 256 CUs x 8 resident), at most one per chunk
-  int parts = std::max(1, std::min(maxchunks, (8192 + nprogs - 1) / nprogs));
-  const long long waves = static_cast<long long>(nprogs) * parts;
-  // waves per SIMD the LDS allows (NS x 8 KiB per wave) bound the registers: 1 slot -> 4, 2 -> 2, 3 -> 1
-#define PGX_WAVE_LAUNCH(NS, WPB, MINW)                                                                             \
-  hipLaunchKernelGGL((pgx::pgx_roaring_program_wave<NS, WPB, MINW>),                                              \
-                     dim3(static_cast<unsigned>((waves + WPB - 1) / WPB)), dim3(64 * WPB),                        \
-                     static_cast<size_t>(NS) * WPB * 2048 * 4, stream, progs, descs, nprogs, parts)
-  if (nslots <= 1) PGX_WAVE_LAUNCH(1, 4, 4);
-  else if (nslots == 2) PGX_WAVE_LAUNCH(2, 2, 2);
-  else PGX_WAVE_LAUNCH(3, 2, 1);
-#undef PGX_WAVE_LAUNCH
-  return hipGetLastError();
-}
-
-extern "C" hipError_t pgx_launch_roaring_program(const pgx::RProg* progs, const pgx::RDesc* descs, int nprogs,
-                                                 int maxchunks, int maxleaves, hipStream_t stream) {
-  if (nprogs <= 0 || maxchunks <= 0) return hipSuccess;
-  const long long blocks = static_cast<long long>(nprogs) * maxchunks;
-  if (maxleaves < 0 && -maxleaves <= pgx::kRProgMaxLeaves) {  // per-segment walk (host: every program <= 512 bitmaps)
-    // at least ~2048 workgroups (two full rounds at 4 resident per CU on 256 CUs), at most 8 parts per segment
-    int parts = std::max(1, std::min(std::min(maxchunks, 8), (2048 + nprogs - 1) / nprogs));
-      hipLaunchKernelGGL(pgx::pgx_roaring_program_seg, dim3(static_cast<unsigned>(nprogs * parts)),
-                       dim3(pgx::kSegRThreads), static_cast<size_t>(-maxleaves) * 2048 * 4, stream, progs, descs,
-                       nprogs, parts);
-    return hipGetLastError();
-  }
-  if (maxleaves >= 1 && maxleaves <= pgx::kRProgMaxLeaves) {
-    hipLaunchKernelGGL(pgx::pgx_roaring_program_wide, dim3(static_cast<unsigned>(blocks)), dim3(256),
-                       static_cast<size_t>(maxleaves) * 2048 * 4, stream, progs, descs, nprogs, maxchunks);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(pgx::pgx_roaring_program, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, progs, descs,
-                     nprogs, maxchunks);
   return hipGetLastError();
 }
 
