@@ -5,6 +5,9 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-functi
 CSRC = pinot_amd/csrc
 HDR = include/pgx.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
 HOST_HDR = $(HDR) $(CSRC)/pgx_host.h
+# what every .hip file includes; SEL_HDR: the walk over the query kernels' selection bits
+DEV_HDR = $(CSRC)/pgx_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+SEL_HDR = $(DEV_HDR) $(CSRC)/pgx_hll_device.h
 
 all: pinot_amd/libpgx.so
 
@@ -21,10 +24,10 @@ build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o bui
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_jit.o: $(CSRC)/pgx_jit.cpp $(HDR) build/pgx_jit_abi.inc build/pgx_roaring_device.inc build/pgx_jit_device.inc
+build/pgx_jit.o: $(CSRC)/pgx_jit.cpp $(HDR) build/pgx_jit_abi.inc build/pgx_device.inc build/pgx_roaring_device.inc build/pgx_jit_device.inc
 	$(HIPCC) $(HIPFLAGS) -Ibuild -c $< -o $@
 
-build/pgx_kernels.o: $(CSRC)/pgx_kernels.hip $(HDR)
+build/pgx_kernels.o: $(CSRC)/pgx_kernels.hip $(HDR) $(DEV_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -32,31 +35,31 @@ build/pgx_stats.o: $(CSRC)/pgx_stats.cpp $(CSRC)/pgx_internal.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_trim.o: $(CSRC)/pgx_trim.hip
+build/pgx_trim.o: $(CSRC)/pgx_trim.hip $(CSRC)/pgx_device.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_merge.o: $(CSRC)/pgx_merge.hip
+build/pgx_merge.o: $(CSRC)/pgx_merge.hip $(CSRC)/pgx_device.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_narrow.o: $(CSRC)/pgx_narrow.hip $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_narrow.o: $(CSRC)/pgx_narrow.hip $(DEV_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_select_hip.o: $(CSRC)/pgx_select.hip $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_select_hip.o: $(CSRC)/pgx_select.hip $(DEV_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(SEL_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_roaring.o: $(CSRC)/pgx_roaring.hip $(CSRC)/pgx_roaring_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_roaring.o: $(CSRC)/pgx_roaring.hip $(CSRC)/pgx_roaring_device.h $(DEV_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-build/pgx_distinct_hip.o: $(CSRC)/pgx_distinct.hip $(CSRC)/pgx_hll_device.h $(CSRC)/pgx_internal.h $(CSRC)/pgx_jit_abi.h
+build/pgx_distinct_hip.o: $(CSRC)/pgx_distinct.hip $(SEL_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

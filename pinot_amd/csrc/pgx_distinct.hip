@@ -28,6 +28,7 @@
 // No workgroup waits on another; all stores are plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
 
+#include "pgx_device.h"
 #include "pgx_hll_device.h"
 #include "pgx_internal.h"
 
@@ -68,11 +69,11 @@ __device__ __forceinline__ void dist_scan(uint32_t* bm, const DistinctItem& A, i
       A, words,
       [&](int64_t w, uint32_t sel) PGX_SEL_OP {
         uint32_t v[32];
-        hll_decode_word(A.bits, A.fwd, w, v);
+        pgx_fwd_decode_word(A.bits, A.fwd, w, v);
         dist_mark_word(bm, A, sel, v);
       },
       [&](int32_t row) PGX_SEL_OP {
-        const uint32_t id = hll_value(A.fwd, row, A.bits);
+        const uint32_t id = pgx_fwd_value(A.fwd, row, A.bits);
         if (id < static_cast<uint32_t>(A.card)) dist_mark(bm, id);
       });
 }
@@ -122,7 +123,7 @@ __device__ __forceinline__ void dist_group_rows(const DistinctGroupItem& G, cons
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t on = 0u - ((sel >> (J0 + j)) & 1u);
-      const uint32_t id = hll_value2(gf, d0 + J0 + j, gb) & on;
+      const uint32_t id = pgx_fwd_value2(gf, d0 + J0 + j, gb) & on;
       const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
       s[j] = hll_mv_fold(g == 0 ? 0u : s[j], gid, mul);
     }
@@ -155,14 +156,14 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_group(const Disti
       A, sel_gcols_ok(G.g, K) ? sel_words(A) : 0,
       [&](int64_t w, uint32_t sel) PGX_SEL_OP {
         uint32_t v[32];
-        hll_decode_word(A.bits, A.fwd, w, v);
+        pgx_fwd_decode_word(A.bits, A.fwd, w, v);
 #pragma unroll
         for (int j = 0; j < 32; ++j) sel &= ~(static_cast<uint32_t>(v[j] >= static_cast<uint32_t>(A.card)) << j);
         dist_group_rows<0>(G, K, sel, static_cast<int32_t>(w * 32), v);
         dist_group_rows<16>(G, K, sel, static_cast<int32_t>(w * 32), v);
       },
       [&](int32_t row) PGX_SEL_OP {
-        const uint32_t id = hll_value(A.fwd, row, A.bits);
+        const uint32_t id = pgx_fwd_value(A.fwd, row, A.bits);
         const uint32_t s = sel_row_slot(G.g, K, row);
         if (id < static_cast<uint32_t>(A.card) && s < slots32) dist_mark(A.out + static_cast<size_t>(s) * bw, id);
       });
@@ -171,7 +172,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_group(const Disti
 // ---- DISTINCTCOUNTMV: every value of every selected doc --------------------------------------------------------------
 // Value rows lo .. lo + N - 1 of an item's value stream marked in bm, in passes of N independent accesses: the dictIds,
 // the bitmap words, then the few atomics.  lo < hi <= total: rows at or past hi take row hi - 1's address and mark
-// nothing, so no load is conditional.  hll_value2 reads the row's dword and the next one: for a row below `total` both
+// nothing, so no load is conditional.  pgx_fwd_value2 reads the row's dword and the next: for a row below `total` both
 // lie inside the stream's allocation (whole tiles of rows and 64 bytes more).
 template <int N>
 __device__ __forceinline__ void dist_mv_batch(uint32_t* bm, const DistinctItem& A, uint32_t lo, uint32_t hi) {
@@ -181,7 +182,7 @@ __device__ __forceinline__ void dist_mv_batch(uint32_t* bm, const DistinctItem& 
   for (int i = 0; i < N; ++i) {
     const uint32_t r = lo + static_cast<uint32_t>(i);
     const uint32_t on = static_cast<uint32_t>(static_cast<int32_t>(r - hi) >> 31);  // r < hi (both below 2^31 + N)
-    const uint32_t id = hll_value2(A.fwd, static_cast<int32_t>(__builtin_elementwise_min(r, hi - 1u)), A.bits);
+    const uint32_t id = pgx_fwd_value2(A.fwd, static_cast<int32_t>(__builtin_elementwise_min(r, hi - 1u)), A.bits);
     const uint32_t t = __builtin_elementwise_min(id, card), d = t - card;  // d == 0: a dictId at or past card
     const uint32_t m = static_cast<uint32_t>(static_cast<int32_t>(d | (0u - d)) >> 31) & on;
     v[i] = (t & m) | ~m;

@@ -32,6 +32,7 @@
 // No workgroup waits on another; all stores are plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
 
+#include "pgx_device.h"
 #include "pgx_hll_device.h"
 #include "pgx_internal.h"
 
@@ -77,7 +78,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer(const HllItem* __rest
         // of gather, register read and compare per row leaves one access in flight per wave): the codes (entry 0
         // stands in for rows that offer nothing, so no load is conditional; a code is never 0), the registers, the few
         // atomics
-        hll_decode_word(A.bits, A.fwd, w, v);
+        pgx_fwd_decode_word(A.bits, A.fwd, w, v);
         hll_gather_codes(A, sel, v);
 #pragma unroll
         for (int j = 0; j < 32; ++j) v[j] = regs[v[j] >> 8] < (v[j] & 0xFFu) ? v[j] : 0u;
@@ -85,7 +86,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer(const HllItem* __rest
         for (int j = 0; j < 32; ++j)
           if (v[j] != 0u) atomicMax(&regs[v[j] >> 8], v[j] & 0xFFu);
       },
-      [&](int32_t row) PGX_SEL_OP { hll_offer(regs, A, hll_value(A.fwd, row, A.bits)); });
+      [&](int32_t row) PGX_SEL_OP { hll_offer(regs, A, pgx_fwd_value(A.fwd, row, A.bits)); });
   __syncthreads();
   const uint32_t r = regs[tid];
   if (r != 0u && A.out[tid] < r) atomicMax(&A.out[tid], r);
@@ -108,7 +109,7 @@ __device__ __forceinline__ void hll_group_rows(const HllGroupItem& G, const HllG
       // on: the row still offers (its code field is not 0); a row that does not reads remap entry 0.
       const uint32_t c16 = v[j] & 0xFFFFu;
       const uint32_t on = static_cast<uint32_t>(static_cast<int32_t>(c16 | (0u - c16)) >> 31);
-      const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
+      const uint32_t id = pgx_fwd_value2(gf, d0 + j, gb) & on;
       const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
       // 32-bit arithmetic throughout (a 64-bit multiply-add carries out into scalar registers too): an id of
       // 65536 or more is outside every key space (bad); below that, slot so far + id * mul < 2^32, saturated to
@@ -146,7 +147,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
         // remap entry 0) folded into the slot, which shares the word with the code (both fit 16 bits); the registers;
         // the few atomics
         uint32_t v[32];
-        hll_decode_word(A.bits, A.fwd, w, v);
+        pgx_fwd_decode_word(A.bits, A.fwd, w, v);
         hll_gather_codes(A, sel, v);
         hll_group_rows<0>(G, K, static_cast<int32_t>(w * 32), v);
         hll_group_rows<16>(G, K, static_cast<int32_t>(w * 32), v);
@@ -154,7 +155,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
       [&](int32_t row) PGX_SEL_OP {
         const uint32_t s = sel_row_slot(G.g, K, row);
         if (s < slots32)  // (a key outside the planned space: never written)
-          hll_offer(A.out + static_cast<size_t>(s) * kHllRegs, A, hll_value(A.fwd, row, A.bits));
+          hll_offer(A.out + static_cast<size_t>(s) * kHllRegs, A, pgx_fwd_value(A.fwd, row, A.bits));
       });
 }
 
@@ -162,7 +163,7 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupI
 // Value rows lo .. lo + N - 1 of an item's value stream offered into regs (256 u32, LDS or HBM), in passes of N
 // independent accesses: the dictIds, the codes, the registers, then the few atomics.  lo < hi <= A.h.total: rows at or
 // past hi take row hi - 1's address and offer nothing (their mask is 0), so no load is conditional.  Masks, not
-// compares, across the loads (hll_gather_codes).  hll_value2 reads the row's dword and the next one: for a row below
+// compares, across the loads (hll_gather_codes).  pgx_fwd_value2 reads the row's dword and the next: for a row below
 // `total` both lie inside the stream's allocation, because padded_fwd_bytes(total, bits) covers whole tiles of rows
 // and 64 bytes more (the second dword of the last row ends at most 8 bytes past total * bits / 8).
 template <int N>
@@ -173,7 +174,7 @@ __device__ __forceinline__ void hll_mv_batch(uint32_t* regs, const HllItem& A, u
   for (int i = 0; i < N; ++i) {
     const uint32_t r = lo + static_cast<uint32_t>(i);
     const uint32_t on = static_cast<uint32_t>(static_cast<int32_t>(r - hi) >> 31);  // r < hi (both below 2^31 + N)
-    const uint32_t id = hll_value2(A.fwd, static_cast<int32_t>(__builtin_elementwise_min(r, hi - 1u)), A.bits);
+    const uint32_t id = pgx_fwd_value2(A.fwd, static_cast<int32_t>(__builtin_elementwise_min(r, hi - 1u)), A.bits);
     const uint32_t t = __builtin_elementwise_min(id, nc), d = t - nc;  // d == 0: a dictId at or past the table
     m[i] = static_cast<uint32_t>(static_cast<int32_t>(d | (0u - d)) >> 31) & on;
     v[i] = t & m[i];

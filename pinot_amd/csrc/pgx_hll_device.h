@@ -1,6 +1,6 @@
 // libpgx: device code shared by the kernels that run over the query kernels' selection bits (pgx_hll.hip,
-// pgx_distinct.hip): reading rows of a packed big-endian fixed-bit forward index, one at a time or a whole mask word's
-// 32 rows at once; folding group columns' global ids into a dense slot; and the walk itself -- an item's 32-doc mask
+// pgx_distinct.hip), on top of the forward-index readers of pgx_device.h (one row at a time or a whole mask word's 32
+// rows at once): folding group columns' global ids into a dense slot; and the walk itself -- an item's 32-doc mask
 // words strided over a workgroup, zero words skipped, dense words decoded whole and sparse ones row by row, multi-value
 // columns as runs of docs that own ranges of the value stream, under GROUP BY with the docs' slots parked in LDS.  The
 // walk is a template over the item type; what happens to a word, a row or a batch of value rows is the caller's
@@ -11,71 +11,10 @@
 
 #include <type_traits>
 
+#include "pgx_device.h"
 #include "pgx_internal.h"
 
 namespace pgx {
-
-__device__ __forceinline__ uint32_t hll_value(const uint32_t* __restrict__ fwd, int32_t row, int bits) {
-  const int64_t o = static_cast<int64_t>(row) * bits;
-  const uint32_t* w = fwd + (o >> 5);
-  const int s = static_cast<int>(o & 31);
-  const uint32_t mask = bits == 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-  const uint32_t hi = __builtin_bswap32(w[0]);
-  if (s + bits <= 32) return (hi >> (32 - s - bits)) & mask;  // (the next word may lie past the index: never read)
-  const uint64_t x = (static_cast<uint64_t>(hi) << 32) | __builtin_bswap32(w[1]);
-  return static_cast<uint32_t>(x >> (64 - s - bits)) & mask;
-}
-
-// The same without a branch: both dwords are always read.  For rows inside the padded index only (whole tiles plus 64
-// bytes: the second dword of the last row is still inside).
-__device__ __forceinline__ uint32_t hll_value2(const uint32_t* __restrict__ fwd, int32_t row, int bits) {
-  const int64_t o = static_cast<int64_t>(row) * bits;
-  const uint32_t* w = fwd + (o >> 5);
-  const int s = static_cast<int>(o & 31);
-  const uint64_t x = (static_cast<uint64_t>(__builtin_bswap32(w[0])) << 32) | __builtin_bswap32(w[1]);
-  return static_cast<uint32_t>((x << s) >> (64 - bits));
-}
-
-// The 32 dictIds of one mask word's rows of a B-bit forward index: B dwords, every one read once (streaming), then
-// constant-shift extraction (the layout of pgx_select.hip sel_decode32).
-template <int B>
-__device__ __forceinline__ void hll_decode32(const uint32_t* __restrict__ p, uint32_t (&v)[32]) {
-  uint32_t w[B + 1];
-#pragma unroll
-  for (int i = 0; i < B; ++i) w[i] = __builtin_bswap32(__builtin_nontemporal_load(p + i));
-  w[B] = 0;
-  constexpr uint32_t MASK = (B == 32) ? 0xFFFFFFFFu : ((1u << (B & 31)) - 1u);
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    const int o = j * B, k = o >> 5, sh = o & 31;
-    if (sh + B <= 32) {
-      v[j] = (w[k] >> (32 - sh - B)) & MASK;
-    } else {
-      const uint64_t win = (static_cast<uint64_t>(w[k]) << 32) | w[k + 1];
-      v[j] = static_cast<uint32_t>(win >> (64 - sh - B)) & MASK;
-    }
-  }
-}
-
-#define PGX_HLL_CASES(X) \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-  X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
-__device__ __forceinline__ void hll_decode_word(int bits, const uint32_t* __restrict__ fwd, int64_t word,
-                                                uint32_t (&v)[32]) {
-  const uint32_t* p = fwd + word * bits;
-  switch (bits) {
-#define PGX_HLL_CASE(b)    \
-  case b:                  \
-    hll_decode32<b>(p, v); \
-    break;
-    PGX_HLL_CASES(PGX_HLL_CASE)
-#undef PGX_HLL_CASE
-    default:
-#pragma unroll
-      for (int j = 0; j < 32; ++j) v[j] = 0;
-  }
-}
 
 constexpr int kHllDenseRows = 8;  // selected rows of a mask word from which the whole word's column is decoded
 
@@ -95,7 +34,7 @@ __device__ __forceinline__ uint32_t hll_mv_fold(uint32_t prev, uint32_t gid, uin
 __device__ __forceinline__ uint32_t sel_row_slot(const HllGCol* gc, const HllGroupKey& K, int32_t row) {
   uint32_t s = 0u;
   for (int g = 0; g < K.ngcols; ++g) {
-    const uint32_t id = hll_value(gc[g].fwd, row, gc[g].bits);
+    const uint32_t id = pgx_fwd_value(gc[g].fwd, row, gc[g].bits);
     const uint32_t gid = gc[g].remap ? static_cast<uint32_t>(gc[g].remap[id]) : id;  // a negative id: >= 2^31
     s = hll_mv_fold(s, gid, static_cast<uint32_t>(K.gmul[g]));
   }
@@ -222,7 +161,7 @@ __device__ __forceinline__ void sel_mv_group_walk(const Item& A, const HllGCol* 
 #pragma unroll 8
         for (int j = 0; j < 32; ++j) {
           const uint32_t on = 0u - ((sel >> j) & 1u);
-          const uint32_t id = hll_value2(gf, d0 + j, gb) & on;
+          const uint32_t id = pgx_fwd_value2(gf, d0 + j, gb) & on;
           const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
           mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
         }
@@ -230,7 +169,7 @@ __device__ __forceinline__ void sel_mv_group_walk(const Item& A, const HllGCol* 
         for (uint32_t m = sel; m;) {
           const int j = __builtin_ctz(m);
           m &= m - 1u;
-          const uint32_t id = hll_value(gf, d0 + j, gb);
+          const uint32_t id = pgx_fwd_value(gf, d0 + j, gb);
           const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
           mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
         }

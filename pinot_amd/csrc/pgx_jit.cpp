@@ -40,6 +40,9 @@ namespace {
 const char* kAbiSrc =
 #include "pgx_jit_abi.inc"
     ;
+const char* kDeviceSrc =
+#include "pgx_device.inc"
+    ;
 const char* kRoaringSrc =
 #include "pgx_roaring_device.inc"
     ;
@@ -209,7 +212,7 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
   const bool any_img = lds > 0 && (tab_off != 0 || s.group_mode != G_DENSE_LDS);
 
   Emitter e;
-  e.o << kAbiSrc << "\n" << kRoaringSrc << "\n" << kDevSrc << "\n";
+  e.o << kAbiSrc << "\n" << kDeviceSrc << "\n" << kRoaringSrc << "\n" << kDevSrc << "\n";
   e.ln("#define PT ", s.T);
   e.ln("#define PR ", s.R);
   e.ln("#define PTL ", s.TL);

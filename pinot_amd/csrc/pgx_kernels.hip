@@ -1,7 +1,7 @@
 // MI355X (gfx950) kernels of the pinot-core segment query hot path.
 //
 // One fused kernel (pgx_scan_kernel) replaces the reference's per-doc Java loops for a whole query:
-//   a-1  fixed-bit forward-index decode     (util/PinotDataCustomBitSet.java:122-155)        -> decode32<B>
+//   a-1  fixed-bit forward-index decode     (util/PinotDataCustomBitSet.java:122-155)        -> pgx_fwd_decode32<B>
 //   a-6  scan predicates                    (operator/dociditerators/SVScanDocIdIterator.java) -> leaf words
 //   a-8  sorted-index ranges                (operator/filter/SortedInvertedIndexBasedFilterOperator.java) -> leaf words
 //   a-9/a-10 AND / OR doc-set algebra       (operator/docidsets/{And,Or}BlockDocIdSet.java)    -> bitwise ops on words
@@ -24,86 +24,10 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "pgx_device.h"
 #include "pgx_internal.h"
 
 namespace pgx {
-
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// ---------------------------------------------------------------------------------------------
-// K1: fixed-bit unpack.  The lane's 32 rows occupy B dwords starting at dword (row0/32)*B of the (big-endian,
-// MSB-first) forward index.  Loads are as wide as the lane chunk's alignment allows.
-// ---------------------------------------------------------------------------------------------
-template <int B>
-__device__ __forceinline__ void decode32(const uint32_t* __restrict__ p, uint32_t (&v)[32]) {
-  uint32_t w[B + 1];
-  if constexpr (B % 4 == 0) {
-#pragma unroll
-    for (int i = 0; i < B / 4; ++i) {
-      u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p) + i);
-      w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
-    }
-  } else if constexpr (B % 2 == 0) {
-#pragma unroll
-    for (int i = 0; i < B / 2; ++i) {
-      u32x2 q = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p) + i);
-      w[2 * i] = q.x; w[2 * i + 1] = q.y;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < B; ++i) w[i] = __builtin_nontemporal_load(p + i);
-  }
-  w[B] = 0;
-#pragma unroll
-  for (int i = 0; i < B; ++i) w[i] = bswap32(w[i]);
-  constexpr uint32_t MASK = (B == 32) ? 0xFFFFFFFFu : ((1u << (B & 31)) - 1u);
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    const int o = j * B;
-    const int k = o >> 5;
-    const int s = o & 31;
-    if (s + B <= 32) {
-      v[j] = (w[k] >> (32 - s - B)) & MASK;
-    } else {
-      const uint64_t win = (static_cast<uint64_t>(w[k]) << 32) | w[k + 1];
-      v[j] = static_cast<uint32_t>(win >> (64 - s - B)) & MASK;
-    }
-  }
-}
-
-#define PGX_DECODE_CASES(X) \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-  X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
-__device__ __forceinline__ void decode_dyn(int bits, const uint32_t* __restrict__ fwd, int64_t lane_chunk,
-                                           uint32_t (&v)[32]) {
-  const uint32_t* p = fwd + lane_chunk * bits;
-  switch (bits) {
-#define PGX_CASE(b) \
-  case b:           \
-    decode32<b>(p, v); \
-    break;
-    PGX_DECODE_CASES(PGX_CASE)
-#undef PGX_CASE
-    default:
-#pragma unroll
-      for (int j = 0; j < 32; ++j) v[j] = 0;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Accumulator encodings
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long ord_i64(int64_t x) {
-  return static_cast<unsigned long long>(x) ^ 0x8000000000000000ull;
-}
-__device__ __forceinline__ unsigned long long ord_f64(double d) {
-  unsigned long long b = __double_as_longlong(d);
-  return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Filter leaves
@@ -135,7 +59,7 @@ __device__ __forceinline__ uint32_t leaf_word(const KSeg& S, const KLeaf* xl, co
   if (L.mode == LEAF_RANGES) return ranges_word(L, row0);
   const int c = Q.leaf_col[leaf];
   uint32_t v[32];
-  decode_dyn(S.bits[c], S.fwd[c], lane_chunk, v);
+  pgx_fwd_decode_word(S.bits[c], S.fwd[c], lane_chunk, v);
   uint32_t word = 0;
   if (L.mode == LEAF_SCAN_INTERVAL) {
     const uint32_t lo = static_cast<uint32_t>(L.lo);
@@ -188,125 +112,30 @@ __device__ __forceinline__ uint32_t run_filter(const KSeg& S, const KLeaf* xl, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// Hash table (LONG_MAP / ARRAY_MAP group keys): open addressing, linear probing.
+// Hash table (LONG_MAP / ARRAY_MAP group keys): pgx_device.h pgx_insert.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
 // Probe chains are bounded (kGlobalMaxProbes): at the load factors the host plans (<= 1/2) a longer chain means the
 // table is (nearly) full, so the lane reports overflow at once and the host regrows the table and reruns, instead of
 // walking the whole table with one device atomic per slot.
 constexpr uint64_t kGlobalMaxProbes = 64;
 
-__device__ __forceinline__ int64_t hash_slot64(const KQuery& Q, uint64_t key) {
-  const uint64_t mask = Q.hash_cap - 1;
-  const uint64_t lim = Q.hash_cap < kGlobalMaxProbes ? Q.hash_cap : kGlobalMaxProbes;
-  uint64_t h = mix64(key) & mask;
-  for (uint64_t probe = 0; probe < lim; ++probe) {
-    unsigned long long prev = atomicCAS(Q.keys + h, kEmptyKey, static_cast<unsigned long long>(key));
-    if (prev == kEmptyKey || prev == key) return static_cast<int64_t>(h);
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int64_t hash_slot128(const KQuery& Q, uint64_t klo, uint64_t khi) {
-  const uint64_t mask = Q.hash_cap - 1;
-  const uint64_t lim = Q.hash_cap < kGlobalMaxProbes ? Q.hash_cap : kGlobalMaxProbes;
-  uint64_t h = mix64(klo ^ mix64(khi)) & mask;
-  uint64_t probes = 0;
-  // Every loop iteration makes progress for every lane (no divergent spin on another lane's write).
-  while (probes < lim) {
-    unsigned int st = atomicCAS(Q.key_state + h, 0u, 1u);
-    if (st == 0u) {
-      __hip_atomic_store(Q.keys + 2 * h, klo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(Q.keys + 2 * h + 1, khi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence();
-      atomicExch(Q.key_state + h, 2u);
-      return static_cast<int64_t>(h);
-    }
-    if (st == 2u) {
-      unsigned long long a = __hip_atomic_load(Q.keys + 2 * h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned long long b = __hip_atomic_load(Q.keys + 2 * h + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a == klo && b == khi) return static_cast<int64_t>(h);
-      h = (h + 1) & mask;
-      ++probes;
-    }
-    // st == 1: another lane is publishing this slot; re-read next iteration.
-  }
-  return -1;
-}
-
-// Keys of W 64-bit words (G_HASHW, ARRAY_MAP keys over 126 bits): the 128-bit protocol with W words per slot.
-template <int W>
-__device__ __forceinline__ int64_t hash_slotw(const KQuery& Q, const uint64_t (&k)[W]) {
-  const uint64_t mask = Q.hash_cap - 1;
-  const uint64_t lim = Q.hash_cap < kGlobalMaxProbes ? Q.hash_cap : kGlobalMaxProbes;
-  uint64_t hv = 0;
-#pragma unroll
-  for (int w = 0; w < W; ++w) hv = mix64(hv ^ k[w]);
-  uint64_t h = hv & mask;
-  uint64_t probes = 0;
-  while (probes < lim) {
-    unsigned int st = atomicCAS(Q.key_state + h, 0u, 1u);
-    if (st == 0u) {
-#pragma unroll
-      for (int w = 0; w < W; ++w)
-        __hip_atomic_store(Q.keys + W * h + w, k[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence();
-      atomicExch(Q.key_state + h, 2u);
-      return static_cast<int64_t>(h);
-    }
-    if (st == 2u) {
-      bool same = true;
-#pragma unroll
-      for (int w = 0; w < W; ++w)
-        same = same && __hip_atomic_load(Q.keys + W * h + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k[w];
-      if (same) return static_cast<int64_t>(h);
-      h = (h + 1) & mask;
-      ++probes;
-    }
-  }
-  return -1;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Plane updates (LDS or global; the pointer's address space is known at each call site)
+// Plane values
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void plane_update_global(unsigned long long* p, int op, unsigned long long enc) {
-  switch (op) {
-    case P_ADD_I64: atomicAdd(p, enc); break;
-    case P_ADD_F64: atomicAdd(reinterpret_cast<double*>(p), __longlong_as_double(static_cast<long long>(enc))); break;
-    case P_MIN_ORD: atomicMin(p, enc); break;
-    case P_MAX_ORD: atomicMax(p, enc); break;
-  }
-}
-
 __device__ __forceinline__ unsigned long long value_enc(const void* dict, bool fp, int kind, uint32_t id) {
   if (fp) {
     const double d = static_cast<const double*>(dict)[id];
-    if (kind == A_MIN || kind == A_MAX) return ord_f64(d);
+    if (kind == A_MIN || kind == A_MAX) return pgx_ord_f64(d);
     return static_cast<unsigned long long>(__double_as_longlong(d));
   }
   const int64_t x = static_cast<const int64_t*>(dict)[id];
-  if (kind == A_MIN || kind == A_MAX) return ord_i64(x);
+  if (kind == A_MIN || kind == A_MAX) return pgx_ord_i64(x);
   return static_cast<unsigned long long>(x);
-}
-
-__device__ __forceinline__ unsigned long long combine_enc(int op, unsigned long long x, unsigned long long y) {
-  if (op == P_ADD_I64) return x + y;
-  if (op == P_ADD_F64)
-    return static_cast<unsigned long long>(__double_as_longlong(__longlong_as_double(static_cast<long long>(x)) +
-                                                                __longlong_as_double(static_cast<long long>(y))));
-  if (op == P_MIN_ORD) return x < y ? x : y;
-  return x > y ? x : y;
 }
 
 __device__ __forceinline__ unsigned long long wave_reduce(int op, unsigned long long x) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = combine_enc(op, x, __shfl_xor(x, off));
+  for (int off = 32; off > 0; off >>= 1) x = pgx_plane_combine(op, x, __shfl_xor(x, off));
   return x;
 }
 
@@ -374,7 +203,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         if (mask) {
           const int c = Q.agg_col[a];
           uint32_t v[32];
-          decode_dyn(S.bits[c], S.fwd[c], lane_chunk, v);
+          pgx_fwd_decode_word(S.bits[c], S.fwd[c], lane_chunk, v);
           const bool fp = Q.agg_fp[a];
           if (kind == A_MIN || kind == A_MAX) {
             // Dictionaries are sorted ascending (SegmentDictionaryCreator.build), so the extreme value is the value
@@ -402,11 +231,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         }
         x = wave_reduce(op, x);
         if (lane == 0) {
-          if (op == P_ADD_I64) atomicAdd(&s_acc[a + 1], x);
-          else if (op == P_ADD_F64) atomicAdd(reinterpret_cast<double*>(&s_acc[a + 1]),
-                                              __longlong_as_double(static_cast<long long>(x)));
-          else if (op == P_MIN_ORD) atomicMin(&s_acc[a + 1], x);
-          else atomicMax(&s_acc[a + 1], x);
+          pgx_plane_apply(&s_acc[a + 1], op, x);
         }
       }
     } else {
@@ -424,7 +249,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
       for (int g = 0; g < (GM == G_HASHW ? 0 : Q.num_gcols); ++g) {
         const int c = Q.gcol[g];
         uint32_t v[32];
-        decode_dyn(S.bits[c], S.fwd[c], lane_chunk, v);
+        pgx_fwd_decode_word(S.bits[c], S.fwd[c], lane_chunk, v);
         const int32_t* rm = S.remap[c];
         if (rm) {
 #pragma unroll
@@ -452,7 +277,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         // keys of 3-4 words: 8 rows at a time (their words in registers), each column decoded once per chunk
         for (int j0 = 0; j0 < 32; j0 += 8) {
           if (!((mask >> j0) & 0xFFu)) continue;
-          uint64_t kw[8][kMaxKeyWords];
+          u64 kw[8][kMaxKeyWords];
 #pragma unroll
           for (int r = 0; r < 8; ++r)
 #pragma unroll
@@ -460,7 +285,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
           for (int g = 0; g < Q.num_gcols; ++g) {
             const int c = Q.gcol[g];
             uint32_t v[32];
-            decode_dyn(S.bits[c], S.fwd[c], lane_chunk, v);
+            pgx_fwd_decode_word(S.bits[c], S.fwd[c], lane_chunk, v);
             const int32_t* rm = S.remap[c];
             const int sh = Q.gshift[g], wd = Q.ghi[g];
 #pragma unroll
@@ -478,11 +303,11 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
             if (!((mask >> j) & 1u)) continue;
             int64_t sl;
             if (Q.key_words == 3) {
-              const uint64_t k3[3] = {kw[r][0], kw[r][1], kw[r][2]};
-              sl = hash_slotw<3>(Q, k3);
+              const u64 k3[3] = {kw[r][0], kw[r][1], kw[r][2]};
+              sl = pgx_insert<3>(Q.keys, Q.key_state, Q.hash_cap, k3, kGlobalMaxProbes);
             } else {
-              const uint64_t k4[4] = {kw[r][0], kw[r][1], kw[r][2], kw[r][3]};
-              sl = hash_slotw<4>(Q, k4);
+              const u64 k4[4] = {kw[r][0], kw[r][1], kw[r][2], kw[r][3]};
+              sl = pgx_insert<4>(Q.keys, Q.key_state, Q.hash_cap, k4, kGlobalMaxProbes);
             }
             if (sl < 0) live &= ~(1u << j);
             klo[j] = static_cast<uint64_t>(sl);
@@ -495,8 +320,10 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         for (int j = 0; j < 32; ++j) {
           if ((mask >> j) & 1u) {
             int64_t s;
-            if constexpr (GM == G_HASH64) s = hash_slot64(Q, klo[j]);
-            else s = hash_slot128(Q, klo[j], khi[j]);
+            if constexpr (GM == G_HASH64)
+              s = pgx_insert<1>(Q.keys, Q.key_state, Q.hash_cap, {klo[j]}, kGlobalMaxProbes);
+            else
+              s = pgx_insert<2>(Q.keys, Q.key_state, Q.hash_cap, {klo[j], khi[j]}, kGlobalMaxProbes);
             if (s < 0) live &= ~(1u << j);
             klo[j] = static_cast<uint64_t>(s);
           }
@@ -515,7 +342,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         if (kind == A_COUNT) continue;
         const int c = Q.agg_col[a];
         uint32_t v[32];
-        decode_dyn(S.bits[c], S.fwd[c], lane_chunk, v);
+        pgx_fwd_decode_word(S.bits[c], S.fwd[c], lane_chunk, v);
         const bool fp = Q.agg_fp[a];
         const int op = Q.plane_op[a + 1];
         const uint64_t pbase = static_cast<uint64_t>(a + 1) * stride;
@@ -523,15 +350,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
         for (int j = 0; j < 32; ++j)
           if ((live >> j) & 1u) {
             const unsigned long long e = value_enc(S.dict[c], fp, kind, v[j]);
-            if constexpr (GM == G_DENSE_LDS) {
-              unsigned long long* p = &lds_table[pbase + klo[j]];
-              if (op == P_ADD_I64) atomicAdd(p, e);
-              else if (op == P_ADD_F64) atomicAdd(reinterpret_cast<double*>(p), __longlong_as_double(static_cast<long long>(e)));
-              else if (op == P_MIN_ORD) atomicMin(p, e);
-              else atomicMax(p, e);
-            } else {
-              plane_update_global(&Q.table[pbase + klo[j]], op, e);
-            }
+            pgx_plane_apply(GM == G_DENSE_LDS ? &lds_table[pbase + klo[j]] : &Q.table[pbase + klo[j]], op, e);
           }
       }
     }
@@ -549,7 +368,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
   if constexpr (GM == G_NONE) {
     if (tid < Q.num_planes) {
       const int op = (tid == 0) ? P_ADD_I64 : Q.plane_op[tid];
-      if (tid == 0 || Q.agg_kind[tid - 1] != A_COUNT) plane_update_global(Q.agg_out + tid, op, s_acc[tid]);
+      if (tid == 0 || Q.agg_kind[tid - 1] != A_COUNT) pgx_plane_apply(Q.agg_out + tid, op, s_acc[tid]);
     }
   }
   if constexpr (GM == G_DENSE_LDS) {
@@ -558,7 +377,7 @@ __global__ void __launch_bounds__(kBlock) pgx_scan_kernel(const KQuery Q, int64_
       const uint64_t plane = i / Q.dense_slots;
       const uint64_t s = i - plane * Q.dense_slots;
       if (lds_table[s] == 0) continue;  // slot untouched by this workgroup
-      plane_update_global(Q.table + i, Q.plane_op[plane], lds_table[i]);
+      pgx_plane_apply(Q.table + i, Q.plane_op[plane], lds_table[i]);
     }
   }
 }
@@ -658,21 +477,11 @@ __global__ void __launch_bounds__(256) pgx_compact(const unsigned long long* tab
 }
 
 
-// Global address space (the bitmap kernels, pgx_roaring.hip, define their own).
-#define PGX_GLOBAL __attribute__((address_space(1)))
-
 // ---------------------------------------------------------------------------------------------
 // Multi-value columns.  One thread owns 32 consecutive docs (one mask word); their values are consecutive in the raw
 // section, so neighbouring threads read neighbouring bytes.  A value is cut out of the big-endian bit stream with one
-// 64-bit window (two byte-swapped dwords; the staged buffer is padded past the last value).
+// 64-bit window (pgx_fwd_value2: two byte-swapped dwords; the staged buffer is padded past the last value).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mv_value(const uint32_t* __restrict__ vals, int64_t i, int bits) {
-  const int64_t o = i * bits;
-  const PGX_GLOBAL uint32_t* w = (const PGX_GLOBAL uint32_t*)(vals) + (o >> 5);
-  const uint64_t x = (static_cast<uint64_t>(__builtin_bswap32(w[0])) << 32) | __builtin_bswap32(w[1]);
-  return static_cast<uint32_t>(x >> (64 - (o & 31) - bits)) & (bits == 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u));
-}
-
 __global__ void __launch_bounds__(256) pgx_mv_leaf_mask(const MvLeaf* __restrict__ items, int nitems, int max_words) {
   const int it = static_cast<int>(blockIdx.y);
   if (it >= nitems) return;
@@ -688,19 +497,13 @@ __global__ void __launch_bounds__(256) pgx_mv_leaf_mask(const MvLeaf* __restrict
     const int s = L.start[d0 + k], e = L.start[d0 + k + 1];
     bool hit = false;  // any value in the matching set (EQ / IN / RANGE) or outside it (NEQ / NOT_IN)
     for (int i = s; i < e && !hit; ++i) {
-      const uint32_t v = mv_value(L.vals, i, L.bits);
+      const uint32_t v = pgx_fwd_value2<true>(L.vals, i, L.bits);
       const bool in = L.bitset ? ((L.bitset[v >> 5] >> (v & 31u)) & 1u) : (v - L.lo <= L.span);
       hit = in != (L.neg != 0);
     }
     if (hit != (L.neg != 0)) out |= 1u << k;
   }
   L.mask[w] = out;
-}
-
-__device__ __forceinline__ uint64_t mv_ord_i64(int64_t x) { return static_cast<uint64_t>(x) ^ 0x8000000000000000ull; }
-__device__ __forceinline__ uint64_t mv_ord_f64(double d) {
-  const uint64_t b = static_cast<uint64_t>(__double_as_longlong(d));
-  return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
 }
 
 __global__ void __launch_bounds__(256) pgx_mv_aggregate(const MvAgg* __restrict__ items, int nitems) {
@@ -722,10 +525,10 @@ __global__ void __launch_bounds__(256) pgx_mv_aggregate(const MvAgg* __restrict_
       sel &= sel - 1u;
       const int s = A.start[d0 + k], e = A.start[d0 + k + 1];
       for (int i = s; i < e; ++i) {
-        const uint32_t v = mv_value(A.vals, i, A.bits);
+        const uint32_t v = pgx_fwd_value2<true>(A.vals, i, A.bits);
         ++cnt;
-        if (A.fp) dsum += ((const PGX_GLOBAL double*)A.dict)[v];
-        else isum += ((const PGX_GLOBAL int64_t*)A.dict)[v];
+        if (A.fp) dsum += ((const PGX_G double*)A.dict)[v];
+        else isum += ((const PGX_G int64_t*)A.dict)[v];
         mn = min(mn, v);
         mx = max(mx, v);
       }
@@ -733,10 +536,10 @@ __global__ void __launch_bounds__(256) pgx_mv_aggregate(const MvAgg* __restrict_
   }
   uint64_t omin = ~0ull, omax = 0ull;
   if (cnt) {
-    omin = A.fp ? mv_ord_f64(((const PGX_GLOBAL double*)A.dict)[mn])
-                : mv_ord_i64(((const PGX_GLOBAL int64_t*)A.dict)[mn]);
-    omax = A.fp ? mv_ord_f64(((const PGX_GLOBAL double*)A.dict)[mx])
-                : mv_ord_i64(((const PGX_GLOBAL int64_t*)A.dict)[mx]);
+    omin = A.fp ? pgx_ord_f64(((const PGX_G double*)A.dict)[mn])
+                : pgx_ord_i64(((const PGX_G int64_t*)A.dict)[mn]);
+    omax = A.fp ? pgx_ord_f64(((const PGX_G double*)A.dict)[mx])
+                : pgx_ord_i64(((const PGX_G int64_t*)A.dict)[mx]);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -764,45 +567,6 @@ __global__ void __launch_bounds__(256) pgx_mv_aggregate(const MvAgg* __restrict_
 // them -- receives it (COUNT: 1 per key, CountAggregationFunction.java:81-90; Sum/Min/Max/Avg.aggregateGroupByMV).
 // Keys follow the single-value layouts: dense slot = sum gid_g * mul_g, hash keys gid_g << shift_g.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t mv_slot64(unsigned long long* keys, uint64_t cap, uint64_t key) {
-  const uint64_t mask = cap - 1;
-  const uint64_t lim = cap < kGlobalMaxProbes ? cap : kGlobalMaxProbes;
-  uint64_t h = mix64(key) & mask;
-  for (uint64_t probe = 0; probe < lim; ++probe) {
-    const unsigned long long prev = atomicCAS(keys + h, kEmptyKey, static_cast<unsigned long long>(key));
-    if (prev == kEmptyKey || prev == key) return static_cast<int64_t>(h);
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int64_t mv_slot128(unsigned long long* keys, unsigned int* key_state, uint64_t cap,
-                                              uint64_t klo, uint64_t khi) {
-  const uint64_t mask = cap - 1;
-  const uint64_t lim = cap < kGlobalMaxProbes ? cap : kGlobalMaxProbes;
-  uint64_t h = mix64(klo ^ mix64(khi)) & mask;
-  uint64_t probes = 0;
-  while (probes < lim) {
-    const unsigned int st = atomicCAS(key_state + h, 0u, 1u);
-    if (st == 0u) {
-      __hip_atomic_store(keys + 2 * h, klo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(keys + 2 * h + 1, khi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __threadfence();
-      atomicExch(key_state + h, 2u);
-      return static_cast<int64_t>(h);
-    }
-    if (st == 2u) {
-      const unsigned long long a = __hip_atomic_load(keys + 2 * h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long b = __hip_atomic_load(keys + 2 * h + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a == klo && b == khi) return static_cast<int64_t>(h);
-      h = (h + 1) & mask;
-      ++probes;
-    }
-  }
-  return -1;
-}
-
-
 // The doc's group keys, in generateKeysForDocId* combination order, one callback per key: f(dense slot or packed lo,
 // packed hi).  Returns false when a multi-value group column holds no value (no key).
 template <typename F>
@@ -822,7 +586,7 @@ __device__ __forceinline__ bool mv_for_each_key(const MvGroupArgs& A, const MvGr
       nv[g] = c.start[d + 1] - base[g];
       if (nv[g] <= 0) return false;
     } else {
-      sv[g] = mv_value(c.vals, d, c.bits);
+      sv[g] = pgx_fwd_value2<true>(c.vals, d, c.bits);
     }
   }
   for (;;) {
@@ -831,7 +595,7 @@ __device__ __forceinline__ bool mv_for_each_key(const MvGroupArgs& A, const MvGr
     for (int g = 0; g < kMaxGroupCols; ++g) {
       if (g >= A.ngcols) continue;
       const MvGCol& c = S.g[g];
-      uint32_t id = c.start ? mv_value(c.vals, base[g] + idx[g], c.bits) : sv[g];
+      uint32_t id = c.start ? pgx_fwd_value2<true>(c.vals, base[g] + idx[g], c.bits) : sv[g];
       if (c.remap) id = static_cast<uint32_t>(c.remap[id]);
       if (A.group_mode == G_DENSE_GLOBAL) lo += static_cast<uint64_t>(id) * A.gmul[g];
       else if (A.ghi[g]) hi |= static_cast<uint64_t>(id) << A.gshift[g];
@@ -867,13 +631,13 @@ __global__ void __launch_bounds__(256) pgx_mv_group(const MvGroupArgs* __restric
     const bool fp = A.fp[a] != 0;
     if (fn == MVF_COUNT || fn == MVF_MINMV || fn == MVF_MAXMV) continue;  // MINMV / MAXMV: pgx_mv_group_ordered
     if (fn <= MVF_AVG) {  // single-value column: the doc's value
-      const uint32_t id = mv_value(c.vals, d, c.bits);
+      const uint32_t id = pgx_fwd_value2<true>(c.vals, d, c.bits);
       if (fp) {
         const double v = static_cast<const double*>(c.dict)[id];
-        enc[a] = (fn == MVF_MIN || fn == MVF_MAX) ? ord_f64(v) : static_cast<unsigned long long>(__double_as_longlong(v));
+        enc[a] = (fn == MVF_MIN || fn == MVF_MAX) ? pgx_ord_f64(v) : pgx_f64_bits(v);
       } else {
         const int64_t v = static_cast<const int64_t*>(c.dict)[id];
-        enc[a] = (fn == MVF_MIN || fn == MVF_MAX) ? ord_i64(v) : static_cast<unsigned long long>(v);
+        enc[a] = (fn == MVF_MIN || fn == MVF_MAX) ? pgx_ord_i64(v) : static_cast<unsigned long long>(v);
       }
       continue;
     }
@@ -886,7 +650,7 @@ __global__ void __launch_bounds__(256) pgx_mv_group(const MvGroupArgs* __restric
     double ds = 0.0;  // SUMMV / AVGMV: the doc's values in order (SumMVAggregationFunction.java:98-112)
     int64_t is = 0;
     for (int i = b0; i < b1; ++i) {
-      const uint32_t id = mv_value(c.vals, i, c.bits);
+      const uint32_t id = pgx_fwd_value2<true>(c.vals, i, c.bits);
       if (fp) ds += static_cast<const double*>(c.dict)[id];
       else is += static_cast<const int64_t*>(c.dict)[id];
     }
@@ -895,8 +659,8 @@ __global__ void __launch_bounds__(256) pgx_mv_group(const MvGroupArgs* __restric
   mv_for_each_key(A, S, d, [&](uint64_t lo, uint64_t hi) {
     int64_t slot;
     if (A.group_mode == G_DENSE_GLOBAL) slot = static_cast<int64_t>(lo);
-    else if (A.group_mode == G_HASH64) slot = mv_slot64(A.keys, A.slots, lo);
-    else slot = mv_slot128(A.keys, A.key_state, A.slots, lo, hi);
+    else if (A.group_mode == G_HASH64) slot = pgx_insert<1>(A.keys, A.key_state, A.slots, {lo}, kGlobalMaxProbes);
+    else slot = pgx_insert<2>(A.keys, A.key_state, A.slots, {lo, hi}, kGlobalMaxProbes);
     if (slot < 0) {
       atomicAdd(A.overflow, 1ull);
       return;
@@ -908,43 +672,20 @@ __global__ void __launch_bounds__(256) pgx_mv_group(const MvGroupArgs* __restric
       const int fn = A.fn[a];
       unsigned long long* p = A.table + static_cast<uint64_t>(a + 1) * A.slots + slot;
       const bool fp = A.fp[a] != 0;
+      int op;
       switch (fn) {
-        case MVF_SUM: case MVF_AVG: case MVF_SUMMV: case MVF_AVGMV:
-          if (fp) atomicAdd(reinterpret_cast<double*>(p), __longlong_as_double(static_cast<long long>(enc[a])));
-          else atomicAdd(p, enc[a]);
-          if (fn == MVF_AVGMV)
-            atomicAdd(A.table + static_cast<uint64_t>(A.cnt_plane[a]) * A.slots + slot,
-                      static_cast<unsigned long long>(cnt[a]));
-          break;
-        case MVF_COUNTMV: atomicAdd(p, enc[a]); break;
-        case MVF_MIN: atomicMin(p, enc[a]); break;
-        case MVF_MAX: atomicMax(p, enc[a]); break;
-        default: break;
+        case MVF_SUM: case MVF_AVG: case MVF_SUMMV: case MVF_AVGMV: op = fp ? P_ADD_F64 : P_ADD_I64; break;
+        case MVF_COUNTMV: op = P_ADD_I64; break;
+        case MVF_MIN: op = P_MIN_ORD; break;
+        case MVF_MAX: op = P_MAX_ORD; break;
+        default: continue;
       }
+      pgx_plane_apply(p, op, enc[a]);
+      if (fn == MVF_AVGMV)
+        atomicAdd(A.table + static_cast<uint64_t>(A.cnt_plane[a]) * A.slots + slot,
+                  static_cast<unsigned long long>(cnt[a]));
     }
   });
-}
-
-// Slot of a key pgx_mv_group already inserted (read-only probe; -1 if absent).
-__device__ __forceinline__ int64_t mv_find(const MvGroupArgs& A, uint64_t lo, uint64_t hi) {
-  const uint64_t mask = A.slots - 1;
-  if (A.group_mode == G_HASH64) {
-    uint64_t h = mix64(lo) & mask;
-    for (uint64_t probe = 0; probe < A.slots; ++probe) {
-      const unsigned long long k = A.keys[h];
-      if (k == lo) return static_cast<int64_t>(h);
-      if (k == kEmptyKey) return -1;
-      h = (h + 1) & mask;
-    }
-    return -1;
-  }
-  uint64_t h = mix64(lo ^ mix64(hi)) & mask;
-  for (uint64_t probe = 0; probe < A.slots; ++probe) {
-    if (A.key_state[h] != 2u) return -1;
-    if (A.keys[2 * h] == lo && A.keys[2 * h + 1] == hi) return static_cast<int64_t>(h);
-    h = (h + 1) & mask;
-  }
-  return -1;
 }
 
 // MINMV / MAXMV under GROUP BY (MinMVAggregationFunction.java:76-91 aggregateGroupBySV, :103-119 aggregateGroupByMV;
@@ -972,9 +713,11 @@ __global__ void __launch_bounds__(256) pgx_mv_group_ordered(const MvGroupArgs* _
       if (A.group_mode == G_DENSE_GLOBAL) {
         if (static_cast<int>(lo & 255u) != tid) return;
       } else {
-        const uint64_t own = A.group_mode == G_HASH64 ? mix64(lo) : mix64(lo ^ mix64(hi));
+        // (the probe is bounded by the table alone: the key is there unless pgx_mv_group counted it as overflow)
+        const uint64_t own = A.group_mode == G_HASH64 ? pgx_key_hash<1>({lo}) : pgx_key_hash<2>({lo, hi});
         if (static_cast<int>((own >> 40) & 255u) != tid) return;
-        const int64_t f = mv_find(A, lo, hi);
+        const int64_t f = A.group_mode == G_HASH64 ? pgx_find<1>(A.keys, A.key_state, A.slots, {lo}, A.slots)
+                                                   : pgx_find<2>(A.keys, A.key_state, A.slots, {lo, hi}, A.slots);
         if (f < 0) {
           atomicAdd(A.overflow, 1ull);
           return;
@@ -988,7 +731,7 @@ __global__ void __launch_bounds__(256) pgx_mv_group_ordered(const MvGroupArgs* _
         int64_t* h = hold + a * A.slots + sl;
         const int64_t old = *h;
         for (int i = c.start[d]; i < c.start[d + 1]; ++i) {
-          const int64_t id = mv_value(c.vals, i, c.bits);
+          const int64_t id = pgx_fwd_value2<true>(c.vals, i, c.bits);
           if (fn == MVF_MINMV ? id < old : id > old) *h = id;
         }
       }
@@ -1002,11 +745,10 @@ __global__ void __launch_bounds__(256) pgx_mv_group_ordered(const MvGroupArgs* _
       const int64_t id = hold[a * A.slots + sl];
       if (id == INT64_MAX || id < 0) continue;
       const MvGCol& c = S.a[a];
-      const unsigned long long e = A.fp[a] ? ord_f64(static_cast<const double*>(c.dict)[id])
-                                           : ord_i64(static_cast<const int64_t*>(c.dict)[id]);
+      const unsigned long long e = A.fp[a] ? pgx_ord_f64(static_cast<const double*>(c.dict)[id])
+                                           : pgx_ord_i64(static_cast<const int64_t*>(c.dict)[id]);
       unsigned long long* p = A.table + static_cast<uint64_t>(a + 1) * A.slots + sl;
-      if (fn == MVF_MINMV) atomicMin(p, e);
-      else atomicMax(p, e);
+      pgx_plane_apply(p, fn == MVF_MINMV ? P_MIN_ORD : P_MAX_ORD, e);
     }
 }
 
@@ -1017,11 +759,6 @@ __global__ void __launch_bounds__(256) pgx_mv_group_ordered(const MvGroupArgs* _
 // passes split the records into 64 x 128 partitions by hash bits, and one workgroup per partition aggregates it in an
 // LDS hash table, then appends its groups to compact output arrays.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t part_mix(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
 constexpr int kPartThreads = 1024;
 constexpr int kPartPer = 8;                             // records per thread, held in registers
 constexpr int kPartChunk = kPartThreads * kPartPer;     // records per partitioning workgroup (64 KiB LDS staging)
@@ -1080,7 +817,7 @@ __global__ void __launch_bounds__(kPartThreads) pgx_partition(const uint64_t* __
   const int tid = threadIdx.x;
   const uint64_t bmask = static_cast<uint64_t>(nb - 1);
   for (int i = tid; i < nb; i += kPartThreads) hist[i] = 0;
-  const PGX_GLOBAL uint64_t* src = (const PGX_GLOBAL uint64_t*)(in) +
+  const PGX_G uint64_t* src = (const PGX_G uint64_t*)(in) +
                                    (in_off ? in_off[r] : static_cast<int64_t>(r) * in_cap) + c0;
   uint64_t rec[kPartPer];
 #pragma unroll
@@ -1093,7 +830,7 @@ __global__ void __launch_bounds__(kPartThreads) pgx_partition(const uint64_t* __
   int bk[kPartPer], rk[kPartPer];
 #pragma unroll
   for (int k = 0; k < kPartPer; ++k) {
-    bk[k] = rec[k] == kNoRecord ? -1 : static_cast<int>((part_mix(rec[k] & keymask) >> shift) & bmask);
+    bk[k] = rec[k] == kNoRecord ? -1 : static_cast<int>((pgx_mix64(rec[k] & keymask) >> shift) & bmask);
     rk[k] = bk[k] >= 0 ? atomicAdd(&hist[bk[k]], 1) : 0;
   }
   __syncthreads();
@@ -1111,11 +848,11 @@ __global__ void __launch_bounds__(kPartThreads) pgx_partition(const uint64_t* __
   }
   __syncthreads();
   // copy out bucket runs: consecutive staged records of one bucket go to consecutive output words
-  PGX_GLOBAL uint64_t* dst = (PGX_GLOBAL uint64_t*)(out);
+  PGX_G uint64_t* dst = (PGX_G uint64_t*)(out);
   const int tot = total;
   for (int i = tid; i < tot; i += kPartThreads) {
     const uint64_t v = stage[i];
-    const int b = static_cast<int>((part_mix(v & keymask) >> shift) & bmask);  // recomputed: cheaper than an LDS byte array
+    const int b = static_cast<int>((pgx_mix64(v & keymask) >> shift) & bmask);  // recomputed: cheaper than an LDS byte array
     const unsigned long long p = gpos[b] + static_cast<unsigned long long>(i - offs[b]);
     // plain (not streaming) stores: a bucket run's first and last lines are completed by other workgroups' runs,
     // which L2 merges before write-back
@@ -1162,7 +899,7 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate(const uint64_t
   if (tid == 0) nfound = 0;
   __syncthreads();
   const int64_t n = min(static_cast<int64_t>(in_cnt[static_cast<int64_t>(part) * cstride]), cap);
-  const PGX_GLOBAL uint64_t* src = (const PGX_GLOBAL uint64_t*)(in) + static_cast<int64_t>(part) * cap;
+  const PGX_G uint64_t* src = (const PGX_G uint64_t*)(in) + static_cast<int64_t>(part) * cap;
   const unsigned long long one = PACK ? (1ull << pack_shift) : 0ull;
   bool lost = false;
   for (int64_t base = 0; base < n; base += kAggThreads * kAggPer) {
@@ -1180,7 +917,7 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate(const uint64_t
       if (rec[k] == kNoRecord) continue;
       const uint64_t key = rec[k] & keymask;
       const unsigned int v = static_cast<unsigned int>(rec[k] >> keybits);  // value offset
-      unsigned int bk = static_cast<unsigned int>(part_mix(key)) & (kAggBuckets - 1);
+      unsigned int bk = static_cast<unsigned int>(pgx_mix64(key)) & (kAggBuckets - 1);
       int slot = -1;
       for (int t = 0; t < kAggBuckets;) {
         const ulonglong2* bp = reinterpret_cast<const ulonglong2*>(&tkey[bk * kAggWays]);
@@ -1231,8 +968,8 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate(const uint64_t
     oplane[ocap + o] = static_cast<unsigned long long>(static_cast<int64_t>(sm) + static_cast<int64_t>(c) * vbase);
     const int64_t vlo = vbase + static_cast<int64_t>(lo);
     const int64_t vhi = vbase + static_cast<int64_t>(hi);
-    oplane[2 * ocap + o] = static_cast<unsigned long long>(vlo) ^ 0x8000000000000000ull;
-    oplane[3 * ocap + o] = static_cast<unsigned long long>(vhi) ^ 0x8000000000000000ull;
+    oplane[2 * ocap + o] = pgx_ord_i64(vlo);
+    oplane[3 * ocap + o] = pgx_ord_i64(vhi);
     ++o;
   }
 }
@@ -1270,8 +1007,8 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate_f64(const uint
   if (tid == 0) nfound = 0;
   __syncthreads();
   const int64_t n = min(static_cast<int64_t>(in_cnt[static_cast<int64_t>(part) * cstride]), cap);
-  const PGX_GLOBAL uint64_t* src = (const PGX_GLOBAL uint64_t*)(in) + static_cast<int64_t>(part) * cap;
-  const PGX_GLOBAL double* fd = (const PGX_GLOBAL double*)fdict;
+  const PGX_G uint64_t* src = (const PGX_G uint64_t*)(in) + static_cast<int64_t>(part) * cap;
+  const PGX_G double* fd = (const PGX_G double*)fdict;
   bool lost = false;
   for (int64_t base = 0; base < n; base += kAggThreads * kAggPer) {
     uint64_t rec[kAggPer];
@@ -1287,7 +1024,7 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate_f64(const uint
     for (int k = 0; k < kAggPer; ++k) {
       if (rec[k] == kNoRecord) continue;
       const uint64_t key = rec[k] & keymask;
-      unsigned int bk = static_cast<unsigned int>(part_mix(key)) & (kAggBuckets - 1);
+      unsigned int bk = static_cast<unsigned int>(pgx_mix64(key)) & (kAggBuckets - 1);
       int slot = -1;
       for (int t = 0; t < kAggBuckets;) {
         const ulonglong2* bp = reinterpret_cast<const ulonglong2*>(&tkey[bk * kAggWays]);
@@ -1308,8 +1045,7 @@ __global__ void __launch_bounds__(kAggThreads) pgx_part_aggregate_f64(const uint
       atomicAdd(&tcnt[slot], 1u);
       atomicAdd(&tsum[slot], val[k]);
       if (MN || MX) {
-        const uint64_t b = static_cast<uint64_t>(__double_as_longlong(val[k]));
-        const unsigned long long o = (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+        const unsigned long long o = pgx_ord_f64(val[k]);
         if (MN) atomicMin(&tmin[slot], o);
         if (MX) atomicMax(&tmax[slot], o);
       }
@@ -1375,7 +1111,7 @@ __global__ void pgx_synth_kernel(uint32_t* out_words, int64_t n_rows, int bits, 
       else placed = v >> (-sh);
       word |= static_cast<uint32_t>(placed & 0xFFFFFFFFull);
     }
-    out_words[w] = bswap32(word);
+    out_words[w] = __builtin_bswap32(word);
   }
 }
 
@@ -1396,7 +1132,7 @@ __global__ void pgx_pack_remap_kernel(uint32_t* out_words, const int32_t* __rest
       const int64_t sh = 32 - (r * bits - bit0) - bits;
       word |= static_cast<uint32_t>((sh >= 0 ? v << sh : v >> (-sh)) & 0xFFFFFFFFull);
     }
-    out_words[w] = bswap32(word);
+    out_words[w] = __builtin_bswap32(word);
   }
 }
 

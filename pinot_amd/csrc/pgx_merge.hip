@@ -16,14 +16,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pgx_device.h"
+
 namespace pgx {
 
 constexpr unsigned long long kMergeEmpty = ~0ull;  // packed keys use < 64 bits (pgx_plan.cpp part_keybits <= 63)
-
-__device__ __forceinline__ uint64_t merge_mix(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
+constexpr unsigned int* kNoState = nullptr;        // one-word keys: pgx_insert / pgx_find claim on the key itself
 
 // op: 0 int64 add, 1 double add, 2 ordered-u64 min, 3 ordered-u64 max (PlaneOp); ops packs 2 bits per plane.
 __global__ void pgx_dense_reduce(unsigned long long* __restrict__ dst, const unsigned long long* __restrict__ src,
@@ -32,15 +30,7 @@ __global__ void pgx_dense_reduce(unsigned long long* __restrict__ dst, const uns
   for (uint64_t i = blockIdx.x * static_cast<uint64_t>(blockDim.x) + threadIdx.x; i < n;
        i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
     const int op = static_cast<int>((ops >> (2 * (i / slots))) & 3u);
-    const unsigned long long a = dst[i], b = src[i];
-    unsigned long long r;
-    if (op == 0) r = a + b;
-    else if (op == 1)
-      r = static_cast<unsigned long long>(__double_as_longlong(__longlong_as_double(static_cast<long long>(a)) +
-                                                              __longlong_as_double(static_cast<long long>(b))));
-    else if (op == 2) r = a < b ? a : b;
-    else r = a > b ? a : b;
-    dst[i] = r;
+    dst[i] = pgx_plane_combine(op, dst[i], src[i]);
   }
 }
 
@@ -53,33 +43,16 @@ __global__ void __launch_bounds__(256) pgx_group_merge(const uint64_t* __restric
                                                        int64_t n, unsigned long long* __restrict__ tkey,
                                                        unsigned long long* __restrict__ tpl, uint64_t cap, int nplanes,
                                                        uint64_t ops, unsigned long long* __restrict__ overflow) {
-  const uint64_t mask = cap - 1;  // cap is a power of two
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const unsigned long long k = key[i * es];
-    uint64_t h = merge_mix(k) & mask;
-    int64_t slot = -1;
-    for (uint64_t probe = 0; probe < cap; ++probe) {
-      const unsigned long long prev = atomicCAS(tkey + h, kMergeEmpty, k);
-      if (prev == kMergeEmpty || prev == k) {
-        slot = static_cast<int64_t>(h);
-        break;
-      }
-      h = (h + 1) & mask;
-    }
+    const int64_t slot = pgx_insert<1>(tkey, kNoState, cap, {key[i * es]}, cap);
     if (slot < 0) {
       atomicAdd(overflow, 1ull);
       continue;
     }
     const uint64_t* g = pl + i * es;
     for (int p = 0; p < nplanes; ++p) {
-      const unsigned long long x = static_cast<unsigned long long>(g[p * ps]);
-      unsigned long long* t = tpl + p * cap + slot;
-      const int op = static_cast<int>((ops >> (2 * p)) & 3u);
-      if (op == 0) atomicAdd(t, x);
-      else if (op == 1) atomicAdd(reinterpret_cast<double*>(t), __longlong_as_double(static_cast<long long>(x)));
-      else if (op == 2) atomicMin(t, x);
-      else atomicMax(t, x);
+      pgx_plane_apply(tpl + p * cap + slot, static_cast<int>((ops >> (2 * p)) & 3u), g[p * ps]);
     }
   }
 }
@@ -151,18 +124,10 @@ __global__ void __launch_bounds__(256) pgx_gather_keys(const unsigned long long*
 __global__ void __launch_bounds__(256) pgx_join_build(const uint64_t* __restrict__ okey, int64_t n,
                                                       unsigned long long* __restrict__ tkey,
                                                       int64_t* __restrict__ tidx, uint64_t cap) {
-  const uint64_t mask = cap - 1;
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const unsigned long long k = okey[i];
-    uint64_t h = merge_mix(k) & mask;
-    for (uint64_t probe = 0; probe < cap; ++probe) {
-      if (atomicCAS(tkey + h, kMergeEmpty, k) == kMergeEmpty) {  // keys are distinct: a free slot, never our key
-        tidx[h] = i;
-        break;
-      }
-      h = (h + 1) & mask;
-    }
+    const int64_t h = pgx_insert<1>(tkey, kNoState, cap, {okey[i]}, cap);  // (keys are distinct: always a free slot)
+    if (h >= 0) tidx[h] = i;
   }
 }
 
@@ -172,21 +137,10 @@ __global__ void __launch_bounds__(256) pgx_join_scatter(const uint64_t* __restri
                                                         const int64_t* __restrict__ tidx, uint64_t cap,
                                                         uint64_t* __restrict__ comb, int64_t ccap, int base,
                                                         unsigned long long* __restrict__ miss) {
-  const uint64_t mask = cap - 1;
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const unsigned long long k = okey[i];
-    uint64_t h = merge_mix(k) & mask;
-    int64_t j = -1;
-    for (uint64_t probe = 0; probe < cap; ++probe) {
-      const unsigned long long t = tkey[h];
-      if (t == k) {
-        j = tidx[h];
-        break;
-      }
-      if (t == kMergeEmpty) break;
-      h = (h + 1) & mask;
-    }
+    const int64_t h = pgx_find<1>(tkey, kNoState, cap, {okey[i]}, cap);
+    const int64_t j = h < 0 ? -1 : tidx[h];
     if (j < 0) {
       atomicAdd(miss, 1ull);
       continue;

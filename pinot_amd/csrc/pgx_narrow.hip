@@ -20,18 +20,11 @@
 
 #include <type_traits>
 
+#include "pgx_device.h"
 #include "pgx_internal.h"
-
-#define PGX_GLOBAL __attribute__((address_space(1)))
 
 namespace pgx {
 namespace {
-
-__device__ __forceinline__ void n_lds_barrier() {  // LDS-only ordering: loads in flight are not drained
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Second split.  Bucket b's records: slab w (one per scan workgroup) holds cnt1[b * nwg + w] records (u32 at
@@ -118,13 +111,13 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
     const unsigned long long c = c1[w];
     return static_cast<uint32_t>(c < static_cast<unsigned long long>(cap1) ? c : static_cast<unsigned long long>(cap1));
   };
-  const PGX_GLOBAL uint32_t* glo = (const PGX_GLOBAL uint32_t*)lo + static_cast<int64_t>(b) * nwg * cap1;
-  const PGX_GLOBAL uint16_t* ghi = hi ? (const PGX_GLOBAL uint16_t*)hi + static_cast<int64_t>(b) * nwg * cap1 : nullptr;
-  PGX_GLOBAL uint32_t* gout = (PGX_GLOBAL uint32_t*)out + static_cast<int64_t>(b) * nsub * cap2 * W;
+  const PGX_G uint32_t* glo = (const PGX_G uint32_t*)lo + static_cast<int64_t>(b) * nwg * cap1;
+  const PGX_G uint16_t* ghi = hi ? (const PGX_G uint16_t*)hi + static_cast<int64_t>(b) * nwg * cap1 : nullptr;
+  PGX_G uint32_t* gout = (PGX_G uint32_t*)out + static_cast<int64_t>(b) * nsub * cap2 * W;
   // record i of sub-bucket sb: words [(sb * cap2 + i) * W, + W) of gout; ring slot (sb << rlog) + (i & rmask) likewise
   auto put_out = [&](uint32_t sb, uint32_t i, uint64_t r) {
     const int64_t at = (static_cast<int64_t>(sb) * cap2 + i) * W;
-    if (W == 2) *(PGX_GLOBAL uint64_t*)(gout + at) = r;
+    if (W == 2) *(PGX_G uint64_t*)(gout + at) = r;
     else gout[at] = static_cast<uint32_t>(r);
   };
   auto put_ring = [&](uint32_t slot, uint64_t r) {
@@ -149,7 +142,7 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
     return r;
   };
   auto load = [&](Rd r, uint32_t (&xl)[kN2Per], uint32_t (&xh)[kN2Per]) {
-    const PGX_GLOBAL uint32_t* sl = glo + static_cast<int64_t>(r.w) * cap1;
+    const PGX_G uint32_t* sl = glo + static_cast<int64_t>(r.w) * cap1;
 #pragma unroll
     for (int k = 0; k < kN2Per; ++k) {
       const uint32_t pos = r.c0 + static_cast<uint32_t>(k * kN2Threads + tid);
@@ -180,7 +173,7 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
       sbp[k] = pos < r0.n ? (sb | 0x80000000u) : 0u;
       pp[k] = pos < r0.n ? atomicAdd(&cur[sb], 1u) : 0u;
     }
-    n_lds_barrier();  // A
+    pgx_lds_barrier();  // A
     const uint32_t* const Uc = Ub[par];
     const uint32_t* const Vc = Vb[par];
     if (wave * 64 < nsub) {  // owner lanes: sub-bucket tid
@@ -218,7 +211,7 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
       if (pos < Uc[sb] + (1u << rlog)) put_ring((sb << rlog) + (pos & rmask), rec[k]);
       else if (pos < ucap) put_out(sb, pos, rec[k]);  // past the ring: straight out
     }
-    n_lds_barrier();  // B
+    pgx_lds_barrier();  // B
     {  // four lanes per unit, 16 bytes each; a unit holding positions below V goes record by record
       const uint32_t n = lcnt[par];
       const int g = lane & 3;
@@ -226,10 +219,10 @@ __global__ void __launch_bounds__(kN2Threads) pgx_narrow_split(const uint32_t* _
         const uint32_t sb = lsub[u];
         const uint32_t p0 = lpos[u];
         if (p0 >= ucap) continue;
-        PGX_GLOBAL uint32_t* const dst = gout + (static_cast<int64_t>(sb) * cap2 + p0) * W + 4 * g;
+        PGX_G uint32_t* const dst = gout + (static_cast<int64_t>(sb) * cap2 + p0) * W + 4 * g;
         const uint32_t* const rs = ring + ((sb << rlog) + (p0 & rmask)) * W + 4 * g;
         if (p0 >= Vc[sb]) {
-          *(PGX_GLOBAL na_u32x4*)dst = *(const na_u32x4*)rs;
+          *(PGX_G na_u32x4*)dst = *(const na_u32x4*)rs;
         } else {  // this lane's 4 / W records, each only if it was not stored straight out
           for (int q = 0; q < 4 / W; ++q)
             if (p0 + (4 / W) * g + q >= Vc[sb])
@@ -291,7 +284,7 @@ constexpr int na_threads() {
 }
 
 __device__ __forceinline__ unsigned long long oplane_sum_key(int64_t sum) {  // trim_key(SUM)
-  return static_cast<unsigned long long>(sum) ^ 0x8000000000000000ull;
+  return pgx_ord_i64(sum);
 }
 
 // IMG 4: img_sh packs the block shift (bits 0-4), the offset width b (bits 5-9) and the number of block bases (bits
@@ -347,7 +340,7 @@ pgx_narrow_aggregate(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (LIMG) {
-    const PGX_GLOBAL uint32_t* gi = (const PGX_GLOBAL uint32_t*)img;
+    const PGX_G uint32_t* gi = (const PGX_G uint32_t*)img;
     for (int i = tid; i < img_words; i += kNAThreads) simg[i] = gi[i];
   }
   for (int i = tid; i < kNAWaves * kNASlots; i += kNAThreads) {
@@ -363,7 +356,7 @@ pgx_narrow_aggregate(
   MT* N = tmn + (MN ? wave * kNASlots : 0);
   MT* X = tmx + (MX ? wave * kNASlots : 0);
   uint32_t* C = tcn + (F64 ? wave * kNASlots : 0);
-  const PGX_GLOBAL GT* gtab = (const PGX_GLOBAL GT*)img;  // GATHER: the value table
+  const PGX_G GT* gtab = (const PGX_G GT*)img;  // GATHER: the value table
   const uint32_t rmask = rb2 >= 32 ? 0xFFFFFFFFu : (1u << rb2) - 1u;
   // home bucket of key bits r2 < 2^rb2: (r2 * kNABuckets) >> rb2, as one 32-bit high multiply
   const int hsh = rb2 >= 1 ? 32 - rb2 : 31;
@@ -373,8 +366,8 @@ pgx_narrow_aggregate(
   const unsigned long long one = 1ull << cshift;
   const unsigned long long smask = one - 1ull;
   const int nw = gridDim.x * kNAWaves;
-  const PGX_GLOBAL na_u32x4* src = (const PGX_GLOBAL na_u32x4*)in;
-  const PGX_GLOBAL int64_t* vd = (const PGX_GLOBAL int64_t*)vdict;
+  const PGX_G na_u32x4* src = (const PGX_G na_u32x4*)in;
+  const PGX_G int64_t* vd = (const PGX_G int64_t*)vdict;
   bool lost = false;
 
   auto load = [&](int pp, uint32_t i0, uint32_t nn, uint32_t (&buf)[BW]) {
@@ -454,12 +447,12 @@ pgx_narrow_aggregate(
                           : vd[static_cast<uint32_t>(fn_[q])];
         if (MX) vhi = IMG ? vbase + static_cast<int64_t>(na_img<IMG>(simg, img_sh, static_cast<uint32_t>(fx[q])))
                           : vd[static_cast<uint32_t>(fx[q])];
-        wpl[2 * rstride + o] = static_cast<uint64_t>(vlo) ^ 0x8000000000000000ull;
-        wpl[3 * rstride + o] = static_cast<uint64_t>(vhi) ^ 0x8000000000000000ull;
+        wpl[2 * rstride + o] = pgx_ord_i64(vlo);
+        wpl[3 * rstride + o] = pgx_ord_i64(vhi);
         note(0, c);
         note(1, oplane_sum_key(static_cast<int64_t>(fsc[q] & smask) + static_cast<int64_t>(c) * vbase));
-        note(2, ~(static_cast<uint64_t>(vlo) ^ 0x8000000000000000ull));
-        note(3, static_cast<uint64_t>(vhi) ^ 0x8000000000000000ull);
+        note(2, ~pgx_ord_i64(vlo));
+        note(3, pgx_ord_i64(vhi));
       } else {
         lost = true;
       }
@@ -558,8 +551,7 @@ pgx_narrow_aggregate(
         atomicAdd(&C[slot], 1u);
         if (SUM) atomicAdd(reinterpret_cast<double*>(&S[slot]), gv);
         if (MN || MX) {
-          const uint64_t b = static_cast<uint64_t>(__double_as_longlong(gv));
-          const unsigned long long o = (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+          const unsigned long long o = pgx_ord_f64(gv);
           if (MN) atomicMin(&N[slot], o);
           if (MX) atomicMax(&X[slot], o);
         }

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "pgx_device.h"
 #include "pgx_internal.h"
 #include "pgx_roaring_device.h"
 

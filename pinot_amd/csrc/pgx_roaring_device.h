@@ -1,5 +1,6 @@
 // Device side of the bitmap inverted-index leaves, shared by the library kernels (pgx_roaring.hip) and the query kernels
-// generated at run time (pasted after pgx_jit_abi.h and in front of pgx_jit_device.h).  Builtin types only, no includes.
+// generated at run time (pasted after pgx_jit_abi.h and pgx_device.h -- u32, PGX_G, the LDS-only barriers -- and in
+// front of pgx_jit_device.h).  Builtin types only, no includes.
 //
 // BitmapBasedFilterOperator (operator/filter/BitmapBasedFilterOperator.java:62-92) ORs the RoaringBitmap of every
 // matching dictId (segment/index/readers/BitmapInvertedIndexReader.java:91-117); AndBlockDocIdSet / OrBlockDocIdSet
@@ -10,28 +11,6 @@
 // inside the inverted-index file, so multi-byte fields are read as u16 pairs.
 #ifndef PGX_ROARING_DEVICE_H_
 #define PGX_ROARING_DEVICE_H_
-
-typedef unsigned int u32;
-// Global (HBM) address space: pointers read out of the argument block are generic, and generic (flat) loads share
-// the LDS wait counter, which would make every LDS read wait for the next tile's prefetch (and would serialise the
-// roaring loads with the mask atomics).
-#define PGX_G __attribute__((address_space(1)))
-
-// LDS hand-off between the lanes of ONE wave (no workgroup barrier).
-__device__ __forceinline__ void pgx_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations (lgkmcnt), not for its outstanding
-// global loads or stores, so a prefetch (the next tile's forward index, the next container's fields) and the previous
-// chunk's mask stores stay in flight across it (__syncthreads drains vmcnt).  Global memory is never communicated
-// between the workgroup's threads where it is used.
-__device__ __forceinline__ void pgx_lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 __device__ __forceinline__ u32 pgx_rd16(const unsigned char* p) { return *(const PGX_G unsigned short*)p; }
 __device__ __forceinline__ u32 pgx_rd32(const unsigned char* p) { return pgx_rd16(p) | (pgx_rd16(p + 2) << 16); }

@@ -20,85 +20,16 @@
 // No workgroup waits on another; all stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
+#include "pgx_device.h"
 #include "pgx_internal.h"
 
 namespace pgx {
-
-__device__ __forceinline__ uint32_t sel_value(const uint32_t* __restrict__ fwd, int32_t row, int bits) {
-  const int64_t o = static_cast<int64_t>(row) * bits;
-  const uint32_t* w = fwd + (o >> 5);
-  const int s = static_cast<int>(o & 31);
-  const uint32_t mask = bits == 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-  const uint32_t hi = __builtin_bswap32(w[0]);
-  if (s + bits <= 32) return (hi >> (32 - s - bits)) & mask;  // (the next word may lie past the index: never read)
-  const uint64_t x = (static_cast<uint64_t>(hi) << 32) | __builtin_bswap32(w[1]);
-  return static_cast<uint32_t>(x >> (64 - s - bits)) & mask;
-}
-
-// The 32 dictIds of mask word `word` (rows 32 * word ...) of a B-bit forward index: B dwords loaded at once, then
-// constant-shift extraction (the layout of pgx_kernels.hip decode32).
-typedef uint32_t sel_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t sel_u32x2 __attribute__((ext_vector_type(2)));
-#define PGX_SEL_GLOBAL __attribute__((address_space(1)))
-
-template <int B>
-__device__ __forceinline__ void sel_decode32(const uint32_t* __restrict__ gp, uint32_t (&v)[32]) {
-  // the widest loads the dword count allows, without their natural alignment (the hardware runs in unaligned mode),
-  // streaming: every dword is read once
-  const PGX_SEL_GLOBAL uint32_t* p = (const PGX_SEL_GLOBAL uint32_t*)gp;
-  uint32_t w[B + 1];
-#pragma unroll
-  for (int i = 0; i < B / 4; ++i) {
-    const sel_u32x4 q = __builtin_nontemporal_load((const PGX_SEL_GLOBAL sel_u32x4*)(p + 4 * i));
-    w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
-  }
-  constexpr int r = B % 4, b = B - r;
-  if constexpr (r >= 2) {
-    const sel_u32x2 q = __builtin_nontemporal_load((const PGX_SEL_GLOBAL sel_u32x2*)(p + b));
-    w[b] = q.x; w[b + 1] = q.y;
-  }
-  if constexpr (r % 2 == 1) w[B - 1] = __builtin_nontemporal_load(p + B - 1);
-#pragma unroll
-  for (int i = 0; i < B; ++i) w[i] = __builtin_bswap32(w[i]);
-  w[B] = 0;
-  constexpr uint32_t MASK = (B == 32) ? 0xFFFFFFFFu : ((1u << (B & 31)) - 1u);
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    const int o = j * B, k = o >> 5, sh = o & 31;
-    if (sh + B <= 32) {
-      v[j] = (w[k] >> (32 - sh - B)) & MASK;
-    } else {
-      const uint64_t win = (static_cast<uint64_t>(w[k]) << 32) | w[k + 1];
-      v[j] = static_cast<uint32_t>(win >> (64 - sh - B)) & MASK;
-    }
-  }
-}
-
-#define PGX_SEL_CASES(X) \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-  X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
-__device__ __forceinline__ void sel_decode_word(int bits, const uint32_t* __restrict__ fwd, int64_t word,
-                                                uint32_t (&v)[32]) {
-  const uint32_t* p = fwd + word * bits;
-  switch (bits) {
-#define PGX_SEL_CASE(b)  \
-  case b:                \
-    sel_decode32<b>(p, v); \
-    break;
-    PGX_SEL_CASES(PGX_SEL_CASE)
-#undef PGX_SEL_CASE
-    default:
-#pragma unroll
-      for (int j = 0; j < 32; ++j) v[j] = 0;
-  }
-}
 
 __device__ __forceinline__ uint64_t sel_key(const SelItem& A, int32_t doc) {
   uint64_t key = 0;
   for (int c = 0; c < A.ncols; ++c) {
     const SelCol& col = A.c[c];
-    uint32_t v = sel_value(col.fwd, doc, col.bits);
+    uint32_t v = pgx_fwd_value(col.fwd, doc, col.bits);
     if (col.desc) v = col.card - 1u - v;
     key = (key << col.kbits) | v;
   }
@@ -243,7 +174,7 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_topk(const SelItem* __re
     const bool dense = __builtin_popcount(sel) >= kSelDenseRows;
     uint32_t v[32];
     if (dense) {
-      sel_decode_word(c0bits, c0fwd, w, v);
+      pgx_fwd_decode_word(c0bits, c0fwd, w, v);
 #pragma unroll
       for (int j = 0; j < 32; ++j) v[j] = c0desc ? c0card - 1u - v[j] : v[j];
     }
@@ -262,7 +193,7 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_topk(const SelItem* __re
         for (uint32_t m = sel; m;) {
           const int k = __builtin_ctz(m);
           m &= m - 1u;
-          uint32_t x = sel_value(c0fwd, d0 + k, c0bits);
+          uint32_t x = pgx_fwd_value(c0fwd, d0 + k, c0bits);
           if (c0desc) x = c0card - 1u - x;
           mn = x < mn ? x : mn;
         }
@@ -291,7 +222,7 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_topk(const SelItem* __re
       for (uint32_t m = sel; m;) {
         const int k = __builtin_ctz(m);
         m &= m - 1u;
-        uint32_t x = sel_value(c0fwd, d0 + k, c0bits);
+        uint32_t x = pgx_fwd_value(c0fwd, d0 + k, c0bits);
         if (c0desc) x = c0card - 1u - x;
         surv |= static_cast<uint32_t>(x < t0) << k;
         eq |= static_cast<uint32_t>(x == t0) << k;
@@ -392,7 +323,7 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_gather(const SelGatherCo
   const int item = static_cast<int>(row / K), rank = static_cast<int>(row % K);
   if (rank >= out_cnt[item]) return;  // ranks past the count keep what the caller put there
   const SelGatherCol col = cols[static_cast<int64_t>(item) * ncols + c];
-  out_ids[idx] = static_cast<int32_t>(sel_value(col.fwd, out_doc[row], col.bits));
+  out_ids[idx] = static_cast<int32_t>(pgx_fwd_value(col.fwd, out_doc[row], col.bits));
 }
 
 }  // namespace pgx

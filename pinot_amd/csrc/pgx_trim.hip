@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define PGX_GLOBAL __attribute__((address_space(1)))
+#include "pgx_device.h"
 
 namespace pgx {
 
@@ -60,29 +60,25 @@ __device__ __forceinline__ bool trim_use_cand(const TrimState* st, const TrimSrc
 }
 
 // Larger key = better group.  Plane 0 is the count; `plane` the function's value plane.
-__device__ __forceinline__ uint64_t trim_key(const PGX_GLOBAL uint64_t* pl, int64_t ocap, int64_t i, int kind,
+__device__ __forceinline__ uint64_t trim_key(const PGX_G uint64_t* pl, int64_t ocap, int64_t i, int kind,
                                              int plane) {
-  const PGX_GLOBAL uint64_t* v = pl + static_cast<int64_t>(plane) * ocap;
+  const PGX_G uint64_t* v = pl + static_cast<int64_t>(plane) * ocap;
   switch (kind) {
     case TK_COUNT:
       return pl[i];
     case TK_SUM:
-      return v[i] ^ 0x8000000000000000ull;
+      return pgx_ord_i64(static_cast<int64_t>(v[i]));
     case TK_MIN:
       return ~v[i];
     case TK_MAX:
       return v[i];
-    case TK_SUMF: {  // f64 sum bits -> ordered
-      const uint64_t b = v[i];
-      return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-    }
+    case TK_SUMF:  // f64 sum bits -> ordered
+      return pgx_ord_bits(v[i]);
     default: {  // AVG: the ratio sum / count as an ordered double (AvgPair compares by value)
       const uint64_t c = pl[i];
       const double s = kind == TK_AVGF ? __longlong_as_double(static_cast<long long>(v[i]))
                                        : static_cast<double>(static_cast<int64_t>(v[i]));
-      const double d = c ? s / static_cast<double>(c) : 0.0;
-      const uint64_t b = static_cast<uint64_t>(__double_as_longlong(d));
-      return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
+      return pgx_ord_f64(c ? s / static_cast<double>(c) : 0.0);
     }
   }
 }
@@ -94,7 +90,7 @@ __global__ void __launch_bounds__(256) pgx_trim_range(const uint64_t* __restrict
   __shared__ unsigned long long wmin[4], wmax[4];
   TrimState* st = sts + blockIdx.y;
   const int kind = K.kind[blockIdx.y], plane = K.plane[blockIdx.y];
-  const PGX_GLOBAL uint64_t* pl = (const PGX_GLOBAL uint64_t*)oplane;
+  const PGX_G uint64_t* pl = (const PGX_G uint64_t*)oplane;
   unsigned long long lo = ~0ull, hi = 0ull;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n;
        i += static_cast<int64_t>(gridDim.x) * 256) {
@@ -158,7 +154,7 @@ __global__ void __launch_bounds__(256) pgx_trim_hist(const TrimSrc S, const Trim
   const bool cand = trim_use_cand(st, S);
   const int64_t n = cand ? static_cast<int64_t>(st->n_cand) : S.n;
   if (static_cast<int64_t>(blockIdx.x) * 256 >= n) return;  // (a short candidate list: most workgroups idle)
-  const PGX_GLOBAL uint64_t* ck = (const PGX_GLOBAL uint64_t*)S.ckey + static_cast<int64_t>(blockIdx.y) * S.ccap;
+  const PGX_G uint64_t* ck = (const PGX_G uint64_t*)S.ckey + static_cast<int64_t>(blockIdx.y) * S.ccap;
   __shared__ unsigned int lh[kTrimBins];
   const int tid = threadIdx.x;
   const int kind = K.kind[blockIdx.y], plane = K.plane[blockIdx.y];
@@ -166,7 +162,7 @@ __global__ void __launch_bounds__(256) pgx_trim_hist(const TrimSrc S, const Trim
   __syncthreads();
   const unsigned long long prefix = st->prefix, mask = st->mask;
   const int shift = st->shift;
-  const PGX_GLOBAL uint64_t* pl = (const PGX_GLOBAL uint64_t*)S.oplane;
+  const PGX_G uint64_t* pl = (const PGX_G uint64_t*)S.oplane;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + tid; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
     const uint64_t key = cand ? ck[i] : trim_key(pl, S.ocap, i, kind, plane);
     if ((key & mask) == prefix) atomicAdd(&lh[(key >> shift) & (kTrimBins - 1u)], 1u);
@@ -192,7 +188,7 @@ __global__ void __launch_bounds__(256) pgx_trim_cand(const TrimSrc S, const Trim
   if (st->done) return;  // threshold complete after one digit: the selection reads the planes once
   const int kind = K.kind[blockIdx.y], plane = K.plane[blockIdx.y];
   const unsigned long long prefix = st->prefix;
-  const PGX_GLOBAL uint64_t* pl = (const PGX_GLOBAL uint64_t*)S.oplane;
+  const PGX_G uint64_t* pl = (const PGX_G uint64_t*)S.oplane;
   cidx += static_cast<int64_t>(blockIdx.y) * S.ccap;
   ckey += static_cast<int64_t>(blockIdx.y) * S.ccap;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -295,11 +291,11 @@ __global__ void __launch_bounds__(256) pgx_trim_select(const TrimSrc S, const Tr
   keys += static_cast<int64_t>(blockIdx.y) * cap;
   const unsigned long long thr = st->prefix;
   const long long ties = st->k;
-  const PGX_GLOBAL uint64_t* pl = (const PGX_GLOBAL uint64_t*)S.oplane;
+  const PGX_G uint64_t* pl = (const PGX_G uint64_t*)S.oplane;
   const bool cand = trim_use_cand(st, S);
   const int64_t n = cand ? static_cast<int64_t>(st->n_cand) : S.n;
-  const PGX_GLOBAL uint64_t* ck = (const PGX_GLOBAL uint64_t*)S.ckey + static_cast<int64_t>(blockIdx.y) * S.ccap;
-  const PGX_GLOBAL int64_t* ci = (const PGX_GLOBAL int64_t*)S.cidx + static_cast<int64_t>(blockIdx.y) * S.ccap;
+  const PGX_G uint64_t* ck = (const PGX_G uint64_t*)S.ckey + static_cast<int64_t>(blockIdx.y) * S.ccap;
+  const PGX_G int64_t* ci = (const PGX_G int64_t*)S.cidx + static_cast<int64_t>(blockIdx.y) * S.ccap;
   auto orig = [&](int64_t i) -> int64_t { return cand ? ci[i] : i; };  // the group's index in the planes
   const int lane = threadIdx.x & 63;
   const unsigned long long below = (1ull << lane) - 1ull;

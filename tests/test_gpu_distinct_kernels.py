@@ -498,3 +498,24 @@ def test_launchers_refuse_bad_arguments(dk):
                  (t, 100, r, o, 4, 4, hp, op, 16, 0, 1), (t, 100, r, o, 4, 4, hp, op, 16, 1025, 1)):
         assert dk.k["emit"](*args, dk.stream) == D.INVALID_VALUE
     assert (dk.back(out, 16) == S32).all()
+
+
+def test_every_stored_width(dk):
+    """Widths 1 .. 32 over 100 docs (three full mask words and a partial one), each with a sparse selection (three
+    rows of every word, the index's last row among them: rows are read one by one) and a dense one (whole words are
+    decoded).  Half the ids use the whole width, so a wrongly cut row marks another bit or lands past card."""
+    rng = np.random.default_rng(18)
+    n = 100
+    sparse = np.zeros(n, bool)
+    sparse[[1, 17, 31, 32, 40, 63, 64, 77, 95, 96, 98, n - 1]] = True
+    items, pre = [], []
+    for bits in range(1, 33):
+        card = min(1 << bits, 1 << 16)
+        ids = np.where(rng.random(n) < 0.5, rng.integers(0, card, n).astype(np.uint64),
+                       rng.integers(0, 1 << bits, n, dtype=np.uint64))
+        ids[n - 1] = card - 1
+        for sel in (sparse, np.ones(n, bool)):
+            items.append({"selected": sel, "ids": ids, "bits": bits, "card": card, "out": len(items)})
+            pre.append(np.zeros(D.words(card), np.uint32))
+    got = _check(dk, items, pre, wgs=2)
+    assert all(g.any() for g in got)

@@ -348,3 +348,27 @@ def test_launchers_refuse_bad_arguments(hk):
         assert (got == gpre).all()
     # no items: nothing to launch, success
     assert hk.offer(hk.up(np.zeros(64, np.uint8)).data_ptr(), C.addressof((R.HllItem * 1)()), 0, 1, hk.stream) == 0
+
+
+def test_every_stored_width(hk):
+    """Widths 1 .. 32 over 100 docs (three full mask words and a partial one), each with a sparse selection (three
+    rows of every word, the index's last row among them: rows are read one by one) and a dense one (whole words are
+    decoded).  Half the ids use the whole width, so a wrongly cut row lands past the table (or on another code)."""
+    rng = np.random.default_rng(17)
+    n = 100
+    sparse = np.zeros(n, bool)
+    sparse[[1, 17, 31, 32, 40, 63, 64, 77, 95, 96, 98, n - 1]] = True
+    items, model_items = [], []
+    for bits in range(1, 33):
+        card = min(1 << bits, 1 << 16)
+        ids = np.where(rng.random(n) < 0.5, rng.integers(0, card, n).astype(np.uint64),
+                       rng.integers(0, 1 << bits, n, dtype=np.uint64))
+        ids[n - 1] = card - 1
+        codes = _table(rng, card)
+        for sel in (sparse, np.ones(n, bool)):
+            items.append({"selected": sel, "ids": ids, "bits": bits, "codes": codes, "out": len(items)})
+            model_items.append(dict(items[-1], selected=sel & (ids < card), ids=np.minimum(ids, card - 1)))
+    pre = [np.zeros(R.REGS, np.uint32) for _ in items]
+    got = _run(hk, items, pre, 2)
+    for g, e in zip(got, _model(model_items, pre)):
+        np.testing.assert_array_equal(g, e)

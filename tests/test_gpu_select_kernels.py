@@ -274,3 +274,25 @@ def test_gather(sk):
             exp = ids[i][j][docs[i * k:i * k + counts[i]]].astype(np.uint32).view(np.int32)
             np.testing.assert_array_equal(out[j, i, :counts[i]], exp)
             assert (out[j, i, counts[i]:] == S32).all()
+
+
+def _width_selections(n=100):
+    """Over n = 100 docs (three full mask words and a partial one): a sparse selection (three rows of every word, the
+    index's last row among them: rows are read one by one) and a dense one (every row: whole words are decoded)."""
+    sparse = np.zeros(n, bool)
+    sparse[[1, 17, 31, 32, 40, 63, 64, 77, 95, 96, 98, n - 1]] = True
+    return sparse, np.ones(n, bool)
+
+
+def test_every_stored_width(sk):
+    """Widths 1 .. 32 of the first order column, whose ids use the whole width: K = num_docs, so the answer is every
+    selected row in key order and any wrongly decoded row moves."""
+    rng = np.random.default_rng(16)
+    n = 100
+    items = []
+    for bits in range(1, 33):
+        card = (1 << bits) if bits < 32 else (1 << 32) - 1
+        for sel in _width_selections(n):
+            items.append({"selected": sel, "cols": [_col(rng.integers(0, card, n, dtype=np.uint64), card, kbits=bits)]})
+    got, _ = _check(sk, items, n, wgs=1)
+    assert [len(g) for g in got] == [12, n] * 32
