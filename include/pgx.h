@@ -41,7 +41,8 @@ extern "C" {
                               * every device-resident layout (several value columns, f64 sums); pgx_select_compile and
                               * pgx_result_select_* were added under 8: new entry points only, no existing struct or
                               * call changed; likewise PGX_DISTINCTCOUNTHLL[MV], pgx_result_hll and pgx_hll_codes, and
-                              * PGX_DISTINCTCOUNT[MV], pgx_result_distinct[_counts] and pgx_java_hash_codes */
+                              * PGX_DISTINCTCOUNT[MV], pgx_result_distinct[_counts] and pgx_java_hash_codes, and
+                              * PGX_PERCENTILE[MV], pgx_result_percentile[_counts] and pgx_histogram_percentile */
 
 typedef enum {
   PGX_OK = 0,
@@ -63,11 +64,16 @@ typedef enum { PGX_INT = 0, PGX_LONG = 1, PGX_FLOAT = 2, PGX_DOUBLE = 3, PGX_STR
  * is the same over every value of a multi-value column in the selected docs.
  * PGX_DISTINCTCOUNT (DistinctCountAggregationFunction.java) and PGX_DISTINCTCOUNTMV (DistinctCountMVAggregationFunction
  * .java) are the exact forms: the intermediate is the set of those hash codes, read with pgx_result_distinct_counts and
- * pgx_result_distinct (below, "DISTINCTCOUNT"). */
+ * pgx_result_distinct (below, "DISTINCTCOUNT").
+ * PGX_PERCENTILE (PercentileAggregationFunction.java) and PGX_PERCENTILEMV (PercentileMVAggregationFunction.java): the
+ * intermediate is the multiset of the selected values, held as (value, count) pairs and read with
+ * pgx_result_percentile_counts and pgx_result_percentile (below, "PERCENTILE").  The multi-value form has the lower
+ * code on purpose: code 14 on a single-value column is refused at compile time. */
 typedef enum { PGX_COUNT = 0, PGX_SUM = 1, PGX_MIN = 2, PGX_MAX = 3, PGX_AVG = 4,
                PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9,
                PGX_DISTINCTCOUNTHLL = 10, PGX_DISTINCTCOUNTHLLMV = 11,
-               PGX_DISTINCTCOUNT = 12, PGX_DISTINCTCOUNTMV = 13 } pgx_agg_fn;
+               PGX_DISTINCTCOUNT = 12, PGX_DISTINCTCOUNTMV = 13,
+               PGX_PERCENTILEMV = 14, PGX_PERCENTILE = 15 } pgx_agg_fn;
 
 /* Predicate kinds (common/Predicate.java Type); they select the physical filter operator exactly as
  * plan/FilterPlanNode.java:118-132 does and drive the numEntriesScannedInFilter statistic. */
@@ -442,6 +448,44 @@ pgx_status pgx_result_distinct(const pgx_result* r, int32_t agg_index, int64_t f
  * UTF-16 code units.  Arguments and checks as for pgx_hll_codes. */
 pgx_status pgx_java_hash_codes(int32_t data_type, const void* values, const int32_t* string_offsets, int64_t n,
                                int32_t* hash_codes);
+
+/* ---- PERCENTILE ---------------------------------------------------------------------------------
+ * PGX_PERCENTILE takes a single-value INT, LONG, FLOAT or DOUBLE column, PGX_PERCENTILEMV a multi-value one (every
+ * value of every selected doc).  The intermediate is the multiset of the selected values as doubles (the dictionary's
+ * getDoubleValue), which is all that PercentileAggregationFunction.java's DoubleArrayList holds once
+ * quantile/PercentileUtil.java:40-52 has sorted it (PercentileMVAggregationFunction.java: the same over every value).
+ * The percentile number is not part of the function: PERCENTILE50/90/95/99, the digest of PERCENTILEEST and the
+ * extremes of MINMAXRANGEMV are all reduced from the same histogram by the caller (pgx_histogram_percentile below).
+ * The functions mix with the standard single-value functions and with PGX_DISTINCTCOUNTHLL[MV] and
+ * PGX_DISTINCTCOUNT[MV] in any order and run in the same scan; two of them over one column share one histogram;
+ * statistics are those of the HLL forms, and a column that several of these families name counts once among the
+ * projected ones.
+ * pgx_result_percentile_counts writes the number of distinct values of groups first_group .. first_group + num_groups
+ * - 1, in the order of pgx_result_group_keys (an aggregation-only result has exactly one group).
+ * pgx_result_percentile writes those groups' (value, count) pairs back to back, values ascending within each group and
+ * values that compare equal merged into one entry; group i's pairs start at the sum of the preceding counts.
+ * PGX_ERR_INVALID_ARG: agg_index is not a PGX_PERCENTILE[MV] function, the range lies outside the result, or
+ * `capacity` (in pairs) is smaller than the sum of the counts.  pgx_result_hll and pgx_result_distinct[_counts] refuse a
+ * percentile index; pgx_result_agg, _group_values and _trim refuse it as they refuse an HLL index, and
+ * pgx_result_gather puts value 0 and count 0 there.
+ * pgx_query_compile returns PGX_ERR_UNSUPPORTED for PGX_PERCENTILEMV when every staged segment of the context that
+ * holds the column holds it single-value, and for PGX_PERCENTILE when every one holds it multi-value; a column no
+ * staged segment has compiles, and the execution checks its own segments.
+ * PGX_ERR_UNSUPPORTED (the caller falls back): every limit of the HLL forms above; a STRING column (the reference's
+ * executor cannot hand one to these functions); and counter tables -- 8 bytes per dictId, per group slot and per
+ * distinct dictionary of the executed segments -- of more than PGX_PERCENTILE_MAX_TABLE_BYTES in all. */
+#define PGX_PERCENTILE_MAX_TABLE_BYTES (256u << 20)
+pgx_status pgx_result_percentile_counts(const pgx_result* r, int32_t agg_index, int64_t first_group,
+                                        int64_t num_groups, int64_t* counts);
+pgx_status pgx_result_percentile(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
+                                 double* values, int64_t* value_counts, int64_t capacity);
+/* Host only, no device needed: PercentileUtil.getValueOnQuantile over a histogram.  values: n doubles, strictly
+ * ascending; counts: how often each occurs; *out = element (int)(total * (percentile / 100.0)) of the expanded sorted
+ * multiset.  PGX_ERR_INVALID_ARG: a percentile outside 0..100, a negative count, values not ascending, or an empty
+ * multiset (the reference throws there), or an index at or past the total (percentile 100).  The index is not cut to
+ * 32 bits: counts may sum past 2^31. */
+pgx_status pgx_histogram_percentile(const double* values, const int64_t* counts, int64_t n, int32_t percentile,
+                                    double* out);
 
 /* Dense-table layout for PGX_X_KEEP_DENSE_ON_DEVICE (multi-GPU RCCL merge):
  * slots = product of group cardinalities; buffer = (1 + num_aggs) planes of slots x 8 bytes.

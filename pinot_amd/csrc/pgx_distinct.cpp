@@ -10,7 +10,7 @@
 namespace pgxh {
 
 // The same dictionary: one SharedDict (numeric), or equal staged STRING dictionaries.
-static bool same_dictionary(const StagedColumn& a, const StagedColumn& b) {
+bool same_dictionary(const StagedColumn& a, const StagedColumn& b) {
   if (a.shared || b.shared) return a.shared == b.shared;
   return a.data_type == b.data_type && a.card == b.card && a.dict_hash == b.dict_hash && a.svals == b.svals &&
          a.ivals == b.ivals && a.dvals == b.dvals;

@@ -110,7 +110,9 @@ static void sel_group_columns(pgx_ctx* ctx, SelScan& S) {
 // pgx_hll_offer[_group] then offers every selected row's code, pgx_hll_offer_mv[_group] the code of every value of
 // every selected doc of a multi-value column (DistinctCountHLLMVAggregationFunction.java).  DISTINCTCOUNT and
 // DISTINCTCOUNTMV functions (codes 12, 13) ride the same scan: pgx_distinct.cpp marks their presence bits on the same
-// stream and collects the result's sets afterwards.  Planned afresh every time (no plan cache).
+// stream and collects the result's sets afterwards; PERCENTILE and PERCENTILEMV (codes 15, 14) are the third family:
+// pgx_percentile.cpp counts the selected values per dictId and collects the groups' (value, count) pairs.  Planned
+// afresh every time (no plan cache).
 void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
              const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom) {
   const uint32_t xflags = opts ? opts->flags : 0;
@@ -126,28 +128,31 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   qs.flags |= PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
   qs.agg_fn.clear();
   qs.agg_col.clear();
-  std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1), dist_pos(size_t(na), -1);
+  std::vector<int> sv_pos(size_t(na), -1), hll_pos(size_t(na), -1), dist_pos(size_t(na), -1), pct_pos(size_t(na), -1);
   std::vector<std::string> hcols;  // a column is single-value or multi-value, so the name identifies the block
   std::vector<char> hmv;           // per HLL column: multi-value (DISTINCTCOUNTHLLMV)
   DistinctRun D;                   // DISTINCTCOUNT / DISTINCTCOUNTMV: their columns, bitmaps and items (pgx_distinct.cpp)
+  PercentileRun Q;                 // PERCENTILE / PERCENTILEMV: their columns, counter tables and items (pgx_percentile.cpp)
   for (int a = 0; a < na; ++a) {
     const int f = q.agg_fn[size_t(a)];
-    if (f >= PGX_DISTINCTCOUNTHLL && f <= PGX_DISTINCTCOUNTMV) {
+    if (f >= PGX_DISTINCTCOUNTHLL && f <= PGX_PERCENTILE) {
       const std::string& c = q.agg_col[size_t(a)];
-      const bool mv = f == PGX_DISTINCTCOUNTHLLMV || f == PGX_DISTINCTCOUNTMV;
+      const bool mv = f == PGX_DISTINCTCOUNTHLLMV || f == PGX_DISTINCTCOUNTMV || f == PGX_PERCENTILEMV;
       const bool exact = f == PGX_DISTINCTCOUNT || f == PGX_DISTINCTCOUNTMV;
+      const bool pct = f == PGX_PERCENTILE || f == PGX_PERCENTILEMV;
       for (int s = 0; s < n; ++s) {
         const bool is_mv = segs[s]->col(c).is_mv;
         if (!mv && is_mv)
-          fail(PGX_ERR_UNSUPPORTED, std::string(exact ? "DISTINCTCOUNT" : "DISTINCTCOUNTHLL") + " on multi-value column " + c);
+          fail(PGX_ERR_UNSUPPORTED,
+               std::string(pct ? "PERCENTILE" : exact ? "DISTINCTCOUNT" : "DISTINCTCOUNTHLL") + " on multi-value column " + c);
         if (mv && !is_mv) fail(PGX_ERR_UNSUPPORTED, "multi-value function on single-value column " + c);
       }
-      std::vector<std::string>& cols = exact ? D.cols : hcols;
+      std::vector<std::string>& cols = pct ? Q.cols : exact ? D.cols : hcols;
       auto it = std::find(cols.begin(), cols.end(), c);
-      (exact ? dist_pos : hll_pos)[size_t(a)] = int(it - cols.begin());
+      (pct ? pct_pos : exact ? dist_pos : hll_pos)[size_t(a)] = int(it - cols.begin());
       if (it == cols.end()) {
         cols.push_back(c);
-        (exact ? D.mv : hmv).push_back(mv);
+        (pct ? Q.mv : exact ? D.mv : hmv).push_back(mv);
       }
     } else {
       if (f < PGX_COUNT || f > PGX_AVGMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
@@ -177,6 +182,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: dense key spaces of up to PGX_HLL_MAX_GROUP_SLOTS only");
   const uint64_t slots = ng > 0 ? P.dense_slots : 1;
   distinct_plan(ctx, segs, n, slots, D);  // (refuses tables over PGX_DISTINCT_MAX_TABLE_BYTES before anything runs)
+  percentile_plan(ctx, segs, n, slots, Q);  // (... over PGX_PERCENTILE_MAX_TABLE_BYTES, and STRING columns)
   P.sel_off.assign(size_t(n), 0);
   int64_t words = 0;
   int max_words = 0;
@@ -209,7 +215,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   S.n = n;
   S.ng = ng;
   S.slots = slots;
-  S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size()) * size_t(n));
+  S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size() + Q.cols.size()) * size_t(n));
   S.scanned = scanned;
   S.st = st;
   sel_group_columns(ctx, S);
@@ -231,14 +237,17 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
               pgx_launch_hll_offer_group, "HLL group offers");
   // the DISTINCTCOUNT[MV] marks, on the same stream
   if (!D.cols.empty()) distinct_mark(ctx, S, D);
+  // the PERCENTILE[MV] counts, likewise
+  if (!Q.cols.empty()) percentile_count(ctx, S, Q);
   pgx_result Rs;
   finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
 
   // 3. assemble in the request's order; numEntriesScannedPostFilter counts each HLL column among the projected ones
-  int extra = 0;  // (a column both an HLL and a DISTINCTCOUNT function name counts once)
+  int extra = 0;  // (a column that functions of several families name counts once)
   std::vector<std::string> special = hcols;
-  for (const auto& c : D.cols)
-    if (std::find(hcols.begin(), hcols.end(), c) == hcols.end()) special.push_back(c);
+  for (const auto* cols : {&D.cols, &Q.cols})
+    for (const auto& c : *cols)
+      if (std::find(special.begin(), special.end(), c) == special.end()) special.push_back(c);
   for (const auto& c : special)
     if (std::find(qs.agg_col.begin(), qs.agg_col.end(), c) == qs.agg_col.end() &&
         std::find(q.group_cols.begin(), q.group_cols.end(), c) == q.group_cols.end())
@@ -252,6 +261,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   R->mode = Rs.mode;
   R->hll_pos = hll_pos;
   R->dist_pos = dist_pos;
+  R->pct_pos = pct_pos;
   const int64_t groups = ng > 0 ? Rs.num_groups : 1;
   R->hll_groups = groups;
   R->hll_regs.assign(nh * size_t(groups) * kHllRegs, 0);
@@ -260,6 +270,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     if (nh) hip_check(hipMemcpy(h32.data(), regs.p, h32.size() * 4, hipMemcpyDeviceToHost), "HLL registers D2H");
     for (size_t i = 0; i < h32.size(); ++i) R->hll_regs[i] = uint8_t(h32[i]);
     distinct_collect(ctx, D, std::vector<int64_t>(1, 0), slots, st, R);
+    percentile_collect(ctx, Q, std::vector<int64_t>(1, 0), slots, st, R);
     R->agg_value.assign(size_t(na), 0.0);
     R->agg_count.assign(size_t(na), 0);
     for (int a = 0; a < na; ++a)
@@ -286,6 +297,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   }
   if (groups == 0) {
     distinct_collect(ctx, D, std::vector<int64_t>(), slots, st, R);  // (no groups: the accessors' shapes)
+    percentile_collect(ctx, Q, std::vector<int64_t>(), slots, st, R);
     return;
   }
   // registers of the groups the result holds: their slots from the keys (global id x gmul), narrowed on the device
@@ -303,6 +315,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   for (int64_t i = 0; i < groups; ++i)
     if (gslot[size_t(i)] < 0 || uint64_t(gslot[size_t(i)]) >= slots) fail(PGX_ERR_INTERNAL, "group slot out of range");
   distinct_collect(ctx, D, gslot, slots, st, R);
+  percentile_collect(ctx, Q, gslot, slots, st, R);
   if (nh == 0) return;
   DevBuf sdev(ctx, size_t(groups) * 8), odev(ctx, size_t(groups) * kHllRegs);
   hip_check(hipMemcpyAsync(sdev.p, gslot.data(), size_t(groups) * 8, hipMemcpyHostToDevice, st), "HLL slots H2D");

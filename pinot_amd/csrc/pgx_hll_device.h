@@ -55,6 +55,7 @@ __device__ __forceinline__ bool sel_gcols_ok(const HllGCol* gc, const HllGroupKe
 // the item's limit: dictIds at or past it take no part
 __host__ __device__ __forceinline__ int32_t sel_limit(const HllItem& A) { return A.ncodes; }
 __host__ __device__ __forceinline__ int32_t sel_limit(const DistinctItem& A) { return A.card; }
+__host__ __device__ __forceinline__ int32_t sel_limit(const PercentileItem& A) { return A.card; }
 
 // mask words of an item; an item with a count or width out of range, or an empty code table or dictionary, has no rows
 template <class Item>

@@ -1630,22 +1630,23 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* d, pgx_query** 
     auto q = std::make_unique<pgx_query>();
     for (int a = 0; a < d->num_aggs; ++a) {
       const int fn = d->aggs[a].fn;
-      if (fn < PGX_COUNT || fn > PGX_DISTINCTCOUNTMV) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
+      if (fn < PGX_COUNT || fn > PGX_PERCENTILE) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
       q->agg_fn.push_back(fn);
       const char* c = d->aggs[a].column;
       std::string col = (c && std::strcmp(c, "*") != 0) ? c : "";
       if (fn != PGX_COUNT && col.empty()) fail(PGX_ERR_INVALID_ARG, "aggregation without column");
-      if (fn == PGX_DISTINCTCOUNTHLLMV || fn == PGX_DISTINCTCOUNTMV) {  // known already: single-value wherever staged
+      if (fn == PGX_DISTINCTCOUNTHLLMV || fn == PGX_DISTINCTCOUNTMV || fn == PGX_PERCENTILEMV) {  // known already: single-value wherever staged
         std::lock_guard<std::mutex> g(ctx->kinds_mu);
         auto it = ctx->col_kinds.find(col);
         if (it != ctx->col_kinds.end() && it->second.first > 0 && it->second.second == 0)
           fail(PGX_ERR_UNSUPPORTED, "multi-value function on single-value column " + col);
       }
-      if (fn == PGX_DISTINCTCOUNT) {  // likewise: multi-value wherever it is staged
+      if (fn == PGX_DISTINCTCOUNT || fn == PGX_PERCENTILE) {  // likewise: multi-value wherever it is staged
         std::lock_guard<std::mutex> g(ctx->kinds_mu);
         auto it = ctx->col_kinds.find(col);
         if (it != ctx->col_kinds.end() && it->second.first == 0 && it->second.second > 0)
-          fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNT on multi-value column " + col);
+          fail(PGX_ERR_UNSUPPORTED,
+               std::string(fn == PGX_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT") + " on multi-value column " + col);
       }
       q->agg_col.push_back(fn == PGX_COUNT ? "" : col);
     }

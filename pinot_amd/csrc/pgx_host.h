@@ -155,6 +155,26 @@ extern "C" hipError_t pgx_launch_distinct_emit(const uint32_t* table, int32_t ca
                                                const int64_t* off, int64_t nrows, int64_t slots, const int32_t* hash,
                                                int32_t* out, int64_t capacity, int wgs_per_row, int wgs,
                                                hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count(const pgx::PercentileItem* items, const pgx::PercentileItem* check,
+                                                  int nitems, int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count_group(const pgx::PercentileGroupItem* items,
+                                                        const pgx::PercentileGroupItem* check, int nitems, int ngcols,
+                                                        const uint64_t* gmul, int64_t slots, int wgs_per_item,
+                                                        hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count_mv(const pgx::PercentileMvItem* items,
+                                                     const pgx::PercentileMvItem* check, int nitems, int wgs_per_item,
+                                                     hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count_mv_group(const pgx::PercentileMvGroupItem* items,
+                                                           const pgx::PercentileMvGroupItem* check, int nitems,
+                                                           int ngcols, const uint64_t* gmul, int64_t slots,
+                                                           int wgs_per_item, hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_sizes(const uint64_t* table, int32_t card, const int64_t* rows,
+                                                  int64_t nrows, int64_t slots, uint32_t* sizes, int wgs,
+                                                  hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_emit(const uint64_t* table, int32_t card, const int64_t* rows,
+                                                 const int64_t* off, int64_t nrows, int64_t slots, int32_t* ids,
+                                                 uint64_t* counts, int64_t capacity, int wgs_per_row, int wgs,
+                                                 hipStream_t stream);
 struct pgx_ctx;
 extern "C" void ctx_unref(pgx_ctx* ctx);
 
@@ -792,8 +812,18 @@ struct pgx_result {
   std::vector<std::vector<int64_t>> dist_start;
   std::vector<std::vector<int32_t>> dist_codes;
   bool is_distinct(int fn) const { return size_t(fn) < dist_pos.size() && dist_pos[size_t(fn)] >= 0; }
+  // PERCENTILE[MV] (run_hll, pgx_percentile.cpp): per function its column (-1: another function); per column and group
+  // where its (value, count) pairs start (groups + 1 entries) and the pairs, values ascending and unique per group
+  std::vector<int> pct_pos;
+  int64_t pct_groups = 0;
+  std::vector<std::vector<int64_t>> pct_start;
+  std::vector<std::vector<double>> pct_values;
+  std::vector<std::vector<int64_t>> pct_counts;
+  bool is_percentile(int fn) const { return size_t(fn) < pct_pos.size() && pct_pos[size_t(fn)] >= 0; }
   // a function without a numeric intermediate: pgx_result_agg, _group_values and _trim refuse its index
-  bool is_hll(int fn) const { return (size_t(fn) < hll_pos.size() && hll_pos[size_t(fn)] >= 0) || is_distinct(fn); }
+  bool is_hll(int fn) const {
+    return (size_t(fn) < hll_pos.size() && hll_pos[size_t(fn)] >= 0) || is_distinct(fn) || is_percentile(fn);
+  }
   std::unique_ptr<AsyncState> async;  // declared last: destroyed (joined) before the fields its thread writes
   void ready() const;                 // waits for an async execution; throws its error
   void materialize();
@@ -1167,10 +1197,10 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
 inline bool is_standard_mv_fn(int fn) { return fn >= PGX_COUNTMV && fn <= PGX_AVGMV; }
 // A segment was staged (sign +1) or is being released (-1): its columns in ctx->col_kinds.
 void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign);
-// (DISTINCTCOUNT and DISTINCTCOUNTMV among them: all four run through run_hll and share its limits)
+// (DISTINCTCOUNT[MV] and PERCENTILE[MV] among them: all six run through run_hll and share its limits)
 inline bool query_has_hll(const pgx_query& q) {
   for (int fn : q.agg_fn)
-    if (fn >= PGX_DISTINCTCOUNTHLL && fn <= PGX_DISTINCTCOUNTMV) return true;
+    if (fn >= PGX_DISTINCTCOUNTHLL && fn <= PGX_PERCENTILE) return true;
   return false;
 }
 
@@ -1293,6 +1323,29 @@ void distinct_mark(pgx_ctx* ctx, const SelScan& S, DistinctRun& D);
 // rows: the table row (slot) of every group of the result, in its order
 void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& rows, uint64_t slots, hipStream_t st,
                       pgx_result* R);
+
+// ---- pgx_percentile.cpp: PERCENTILE / PERCENTILEMV inside run_hll ---------------------------------------------------
+// One counter table per (column, distinct dictionary): slots rows of card u64.  Segments whose dictionaries are the
+// same (same_dictionary) add into one table.
+using PercentileItems =
+    SelItems<pgx::PercentileItem, pgx::PercentileGroupItem, pgx::PercentileMvItem, pgx::PercentileMvGroupItem>;
+struct PercentileTable {
+  const StagedColumn* col = nullptr;  // a column that holds the dictionary
+  DevBuf table;
+};
+struct PercentileRun {
+  std::vector<std::string> cols;  // the query's PERCENTILE[MV] columns; mv: the multi-value form
+  std::vector<char> mv;
+  std::vector<std::vector<PercentileTable>> tabs;  // per column
+  std::vector<std::vector<int>> tab_of;            // per column and segment: its table
+  PercentileItems items;                           // the count kernels' items
+};
+bool same_dictionary(const StagedColumn& a, const StagedColumn& b);  // pgx_distinct.cpp
+void percentile_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots, PercentileRun& Q);
+void percentile_count(pgx_ctx* ctx, const SelScan& S, PercentileRun& Q);
+// rows: the table row (slot) of every group of the result, in its order
+void percentile_collect(pgx_ctx* ctx, PercentileRun& Q, const std::vector<int64_t>& rows, uint64_t slots,
+                        hipStream_t st, pgx_result* R);
 
 void parse_star_tree(pgx_segment& seg);
 void stage_column(pgx_ctx* ctx, pgx_segment* seg, const pgx_column_desc& d, bool device_mem, StagedColumn& c);

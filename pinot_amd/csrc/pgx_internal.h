@@ -286,6 +286,40 @@ static_assert(sizeof(DistinctItem) == 40 && sizeof(DistinctGroupItem) == 40 + kM
                   sizeof(DistinctMvItem) == 56 && sizeof(DistinctMvGroupItem) == sizeof(DistinctGroupItem) + 16,
               "tests/distinct_ref.py mirrors these");
 
+// PERCENTILE / PERCENTILEMV value histograms (pgx_percentile.hip; PercentileAggregationFunction): one item per
+// (segment, function), laid out like the DISTINCTCOUNT items.  The state is one u64 counter per dictId, `card` of them
+// per dictionary (under GROUP BY one such row per slot); counters are only ever added to, so items that share `out`
+// combine.
+constexpr int kPercentileLdsCounters = 8192;  // tables of up to 32 KiB of u32 (slots x card) are counted in LDS
+struct PercentileItem {
+  const uint32_t* sel;         // selected docs: bit (d & 31) of word d >> 5 (written by the query kernel)
+  const uint32_t* fwd;         // packed big-endian fixed-bit forward index, padded to whole tiles
+  uint64_t* out;               // card counters; the group kernels: slots rows of card counters
+  int32_t bits;
+  int32_t num_docs;
+  int32_t card;                // dictIds at or past it count nothing
+  int32_t pad;
+};
+struct PercentileGroupItem {
+  PercentileItem d;
+  HllGCol g[kMaxGroupCols];
+};
+struct PercentileMvItem {      // d.fwd is the value stream, doc i owns the value rows start[i] .. start[i + 1] - 1
+  PercentileItem d;
+  const int32_t* start;        // num_docs + 1 ascending entries; entries past index num_docs are never read
+  int32_t total;               // value rows of the stream: rows at or past it are never read, whatever start[] holds
+  int32_t pad;
+};
+struct PercentileMvGroupItem {
+  PercentileGroupItem g;
+  const int32_t* start;
+  int32_t total;
+  int32_t pad;
+};
+static_assert(sizeof(PercentileItem) == 40 && sizeof(PercentileGroupItem) == 40 + kMaxGroupCols * 24 &&
+                  sizeof(PercentileMvItem) == 56 && sizeof(PercentileMvGroupItem) == sizeof(PercentileGroupItem) + 16,
+              "tests/percentile_ref.py mirrors these");
+
 // Statistics automaton over one segment's leaf masks (pgx_kernels.hip pgx_fsm_chunks / pgx_fsm_compose).
 struct FsmSeg {
   const uint32_t* lmask;       // leaf l, row r: bit (r & 31) of word [l * words + (r >> 5)]

@@ -30,9 +30,11 @@ _DT = {"INT": N.PGX_INT, "LONG": N.PGX_LONG, "FLOAT": N.PGX_FLOAT, "DOUBLE": N.P
 _FN = {"count": N.PGX_COUNT, "sum": N.PGX_SUM, "min": N.PGX_MIN, "max": N.PGX_MAX, "avg": N.PGX_AVG,
        "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV,
        "distinctcounthll": N.PGX_DISTINCTCOUNTHLL, "distinctcounthllmv": N.PGX_DISTINCTCOUNTHLLMV,
-       "distinctcount": N.PGX_DISTINCTCOUNT, "distinctcountmv": N.PGX_DISTINCTCOUNTMV}
+       "distinctcount": N.PGX_DISTINCTCOUNT, "distinctcountmv": N.PGX_DISTINCTCOUNTMV,
+       "percentile": N.PGX_PERCENTILE, "percentilemv": N.PGX_PERCENTILEMV}
 _HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # their intermediates are register sets (pgx_result_hll)
 _DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... sets of Java hash codes (pgx_result_distinct)
+_PERCENTILE_FNS = ("percentile", "percentilemv")  # ... (value, count) histograms (pgx_result_percentile)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -754,6 +756,21 @@ def result_distinct(r, fn_index: int, first_group: int = 0, num_groups: int = 1)
     return [set(flat[int(e - c):int(e)]) for c, e in zip(counts[:num_groups], ends)]
 
 
+def result_percentile(r, fn_index: int, first_group: int = 0, num_groups: int = 1) -> List[list]:
+    """pgx_result_percentile_counts and pgx_result_percentile: the value histogram of a PERCENTILE[MV] function per
+    group (one "group" for an aggregation-only result), a list of (float value, int count) ascending by value."""
+    counts = np.zeros(max(num_groups, 1), dtype=np.int64)
+    N.check(N.lib().pgx_result_percentile_counts(r, fn_index, first_group, num_groups, counts.ctypes.data))
+    ends = np.cumsum(counts[:num_groups])
+    total = int(ends[-1]) if num_groups else 0
+    values = np.zeros(max(total, 1), dtype=np.float64)
+    vcounts = np.zeros(max(total, 1), dtype=np.int64)
+    N.check(N.lib().pgx_result_percentile(r, fn_index, first_group, num_groups, values.ctypes.data,
+                                          vcounts.ctypes.data, total))
+    pairs = list(zip(values[:total].tolist(), vcounts[:total].tolist()))
+    return [pairs[int(e - c):int(e)] for c, e in zip(counts[:num_groups], ends)]
+
+
 def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = False) -> IntermediateResultsBlock:
     L = N.lib()
     st = (C.c_int64 * 4)()
@@ -767,6 +784,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
                 continue
             if fn in _DISTINCT_FNS:  # the set of hash codes
                 out.append(result_distinct(r, i)[0])
+                continue
+            if fn in _PERCENTILE_FNS:  # the (value, count) histogram
+                out.append(result_percentile(r, i)[0])
                 continue
             v, c = C.c_double(), C.c_int64()
             N.check(L.pgx_result_agg(r, i, C.byref(v), C.byref(c)))
@@ -800,6 +820,9 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
         if fn in _DISTINCT_FNS:
             vals.append(result_distinct(r, i, 0, n))
             continue
+        if fn in _PERCENTILE_FNS:
+            vals.append(result_percentile(r, i, 0, n))
+            continue
         v = np.zeros(max(n, 1), dtype=np.float64)
         c = np.zeros(max(n, 1), dtype=np.int64)
         N.check(L.pgx_result_group_values(r, i, v.ctypes.data, c.ctypes.data))
@@ -815,7 +838,7 @@ def decode_result(q: _Query, r, segments: Sequence[IndexSegment], trim: bool = F
     if trim:
         trimmed = []
         for i in range(len(q.fns)):
-            if q.fns[i] in _HLL_FNS or q.fns[i] in _DISTINCT_FNS:  # no order to trim by: every group (pgx_result_trim refuses the index)
+            if q.fns[i] in _HLL_FNS + _DISTINCT_FNS + _PERCENTILE_FNS:  # no order to trim by: every group (pgx_result_trim refuses the index)
                 trimmed.append({keys[j]: per_group[j][i] for j in range(n)})
                 continue
             cap = C.c_int64(n)

@@ -11,7 +11,10 @@ decomposed on the host into GPU sub-queries the fused scan kernels already run:
   (operator/aggregation/DefaultAggregationExecutor.java:135-139, common/DataFetcher.java:242-248:
   ``dictionary.get(dictId).hashCode()``), and the function adds ``(int) hash`` (operator/aggregation/function/
   DistinctCountAggregationFunction.java aggregate), so STRING columns are supported and FLOAT 0.25 / 0.75 stay distinct;
-* PERCENTILEnn(c) -> the same ``GROUP BY c`` histogram; intermediate the (value, count) pairs in value order, i.e. the
+* PERCENTILEnn(c), PERCENTILEESTnn(c), their MV forms and MINMAXRANGEMV(c) -> one function of the base query itself per
+  column (PGX_PERCENTILE / PGX_PERCENTILEMV: one counter per dictId on the device, the (value, count) pairs read with
+  pgx_result_percentile; ``native_percentile``).  Where the library refuses the shape, or with PGX_PERCENTILE_NATIVE=0,
+  the same ``GROUP BY c`` histogram; intermediate the (value, count) pairs in value order, i.e. the
   reference's DoubleArrayList of every selected value (PercentileAggregationFunction.java aggregate) held as a multiset;
 * DISTINCTCOUNTHLL(c) -> a function of the base query itself (PGX_DISTINCTCOUNTHLL: the registers are built on the
   device and read with pgx_result_hll; ``native_hll``), and DISTINCTCOUNTHLLMV(c) likewise (PGX_DISTINCTCOUNTHLLMV:
@@ -42,6 +45,9 @@ from .pql import EXT_FUNCTIONS, EXT_MV_FUNCTIONS
 _HIST_FNS = ("distinctcount", "distinctcounthll", "fasthll")
 _NATIVE_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # functions of the base query when `native_hll`
 _NATIVE_DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... when `native_distinct`
+# ... when `native_percentile`: everything reduced from the value histogram of one column
+_NATIVE_PERCENTILE_FNS = tuple("percentile%s%d%s" % (e, p, m) for e in ("", "est") for p in (50, 90, 95, 99)
+                               for m in ("", "mv")) + ("minmaxrangemv",)
 
 
 def base_fn(fn: str) -> str:
@@ -165,15 +171,47 @@ def native_distinct(request: dict, segments) -> bool:
     return not _star_tree_request(request, segments)
 
 
+def native_percentile(request: dict, segments) -> bool:
+    """Whether the request's PERCENTILEnn, PERCENTILEESTnn (also MV) and MINMAXRANGEMV functions read their value
+    histogram from a PGX_PERCENTILE / PGX_PERCENTILEMV function of the base query (pgx_percentile.hip), by
+    ``native_hll``'s rules: PGX_PERCENTILE_NATIVE=0 forces the ``GROUP BY c`` histogram, and a request whose base query
+    a star tree could answer keeps the decomposition."""
+    if os.environ.get("PGX_PERCENTILE_NATIVE", "1") == "0":
+        return False
+    if not any(a["fn"] in _NATIVE_PERCENTILE_FNS for a in request["aggregations"]):
+        return False
+    return not _star_tree_request(request, segments)
+
+
+def _is_hist_slot(s) -> bool:
+    return isinstance(s, tuple) and s[0] == "hist"
+
+
+def _from_native_histogram(fn: str, h):
+    """The intermediate of a `_NATIVE_PERCENTILE_FNS` function from its column's (value, count) pairs, as the
+    decomposition builds it from the ``GROUP BY c`` histogram."""
+    if fn == "minmaxrange":
+        return (float(h[0][0]), float(h[-1][0])) if h else (math.inf, -math.inf)
+    if fn.startswith("percentileest"):
+        return QD.from_histogram(_numeric(h))
+    return _numeric(h)
+
+
 def _base_request(request: dict, native: Sequence[str] = ()):
     """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE, and the functions named
-    in `native`: DISTINCTCOUNTHLL[MV], DISTINCTCOUNT[MV]) and, per original function, its base slot: an index, a
-    (min, max) index pair, or None (histogram functions)."""
+    in `native`: DISTINCTCOUNTHLL[MV], DISTINCTCOUNT[MV], and one PERCENTILE[MV] per column for the functions reduced
+    from its value histogram) and, per original function, its base slot: an index, a (min, max) index pair,
+    ("hist", index) for a native value histogram, or None (histogram sub-query functions)."""
     base = [{"fn": "count", "column": "*"}]
     slot = []
     for a in request["aggregations"]:
         fn = a["fn"]
-        if fn in native:
+        if fn in native and fn in _NATIVE_PERCENTILE_FNS:
+            f = {"fn": "percentilemv" if fn in EXT_MV_FUNCTIONS else "percentile", "column": a["column"]}
+            if f not in base:  # the functions of one column share one histogram
+                base.append(f)
+            slot.append(("hist", base.index(f)))
+        elif fn in native:
             base.append(dict(a))
             slot.append(len(base) - 1)
         elif fn == "minmaxrange":
@@ -273,6 +311,8 @@ def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -
 
     def value(a, s, key, bvals):
         fn = base_fn(a["fn"])
+        if _is_hist_slot(s):
+            return _from_native_histogram(fn, bvals[s[1]])
         if fn == "minmaxrange" and s is None:  # MINMAXRANGEMV: the extremes of the value multiset
             h = hists[a["column"]].get(key, [])
             return (float(h[0][0]), float(h[-1][0])) if h else (math.inf, -math.inf)
@@ -311,15 +351,17 @@ def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -
 
 def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
         combine: bool = True) -> E.IntermediateResultsBlock:
-    """Native where the library takes the shape: first with the HLL and the DISTINCTCOUNT functions in the base query,
-    then with the HLL functions alone (an HLL function keeps its native path when a DISTINCTCOUNT beside it is refused),
-    then the full decomposition."""
-    hll, dist = native_hll(request, segments), native_distinct(request, segments)
+    """Native where the library takes the shape: first with every enabled family in the base query, then without the
+    percentile family, then with the HLL functions alone (an HLL function keeps its native path when a DISTINCTCOUNT
+    beside it is refused), then the full decomposition.  No measured shape ran slower natively than decomposed
+    (tools/bench_percentile.py), so none is routed away beforehand."""
+    families = [(native_percentile(request, segments), _NATIVE_PERCENTILE_FNS),
+                (native_distinct(request, segments), _NATIVE_DISTINCT_FNS),
+                (native_hll(request, segments), _NATIVE_HLL_FNS)]
     routes = []
-    if dist:
-        routes.append(_NATIVE_DISTINCT_FNS + (_NATIVE_HLL_FNS if hll else ()))
-    if hll:
-        routes.append(_NATIVE_HLL_FNS)
+    for i, (on, _) in enumerate(families):
+        if on:
+            routes.append(sum((fns for on_j, fns in families[i:] if on_j), ()))
     for native in routes:
         try:
             return _run(ctx, request, segments, combine, native)
@@ -357,7 +399,9 @@ def _run(ctx, request, segments, combine, native) -> E.IntermediateResultsBlock:
     out = []
     for a, s in zip(aggs, slot):
         fn = base_fn(a["fn"])
-        if fn == "minmaxrange" and s is None:  # MINMAXRANGEMV
+        if _is_hist_slot(s):
+            out.append(_from_native_histogram(fn, base_res[s[1]]))
+        elif fn == "minmaxrange" and s is None:  # MINMAXRANGEMV
             h = hists[a["column"]]
             out.append((float(h[0][0]), float(h[-1][0])) if h else (math.inf, -math.inf))
         elif fn == "minmaxrange":
