@@ -55,6 +55,10 @@ build/pgx_hll_hip.o: $(CSRC)/pgx_hll.hip $(SEL_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+build/pgx_unpack_check.o: $(CSRC)/pgx_unpack_check.hip $(CSRC)/pgx_jit_device.h $(DEV_HDR)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 build/pgx_roaring.o: $(CSRC)/pgx_roaring.hip $(CSRC)/pgx_roaring_device.h $(DEV_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -67,7 +71,7 @@ build/pgx_percentile_hip.o: $(CSRC)/pgx_percentile.hip $(SEL_HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o build/pgx_distinct_hip.o build/pgx_distinct.o build/pgx_percentile_hip.o build/pgx_percentile.o build/pgx_roaring.o
+pinot_amd/libpgx.so: build/pgx_host.o build/pgx_part.o build/pgx_multi.o build/pgx_realtime.o build/pgx_fixtures.o build/pgx_stage.o build/pgx_mv.o build/pgx_plan_cache.o build/pgx_plan.o build/pgx_jit.o build/pgx_kernels.o build/pgx_trim.o build/pgx_stats.o build/pgx_merge.o build/pgx_narrow.o build/pgx_select_hip.o build/pgx_select.o build/pgx_hll_hip.o build/pgx_hll.o build/pgx_distinct_hip.o build/pgx_distinct.o build/pgx_percentile_hip.o build/pgx_percentile.o build/pgx_roaring.o build/pgx_unpack_check.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ -L/opt/rocm/lib -lhiprtc -Wl,-rpath,/opt/rocm/lib -Wl,--no-undefined
 
 # Host-only check of pgx_hash.h (the Java hash codes, the sort + unique union) under AddressSanitizer and UBSan: no device

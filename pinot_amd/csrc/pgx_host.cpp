@@ -662,6 +662,8 @@ void plan_jit(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n,
     J.leafmask = P.fsm_on && P.lmask_off[members[0]] >= 0;
     J.compact = P.rchunk && !P.use_part;  // selective bitmap filters: aggregate the selected rows packed
     J.selmask = P.want_selmask;
+    J.dense_body = P.kn.dense_body;
+    if (P.kn.sparse_k >= 0) J.sparse_k = P.kn.sparse_k;
 
     ExecPlan::JitGroup G;
     G.T = J.T;

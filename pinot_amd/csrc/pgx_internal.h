@@ -450,7 +450,9 @@ constexpr int kNarrowMaxBits2 = 10;  // second split (pgx_narrow_split): up to 1
 //                      narrow_log (which sparse path ran, hash-table regrowth; on stderr), host_profile (planning phases
 //                      on stderr); A/B switches measured slower and kept off: nunit=16 (16-record narrow
 //                      scan units), pf2 (narrow scans load two tiles ahead), noimg (no LDS value images in the query
-//                      kernels), head=N (a lone replay's first part is 1/N of the segments)
+//                      kernels), head=N (a lone replay's first part is 1/N of the segments); A/B switches of the sparse
+//                      tile body: densebody (doc-mask filters run the dense row loop), sparsek=N (a wave
+//                      walks set bits while no lane holds more than N selected rows of a sub-step; default kSparseK)
 // and, outside the query: PGX_PLAN_CACHE=0 (process-wide), PGX_JIT_CACHE=<dir> / PGX_JIT_DUMP=<dir> (the compiler).
 enum RProgKind { RPROG_AUTO = -1, RPROG_OFF = 0, RPROG_WAVE = 1, RPROG_SEG = 2, RPROG_CHUNK = 3, RPROG_STACK = 4 };
 struct Knobs {
@@ -468,6 +470,8 @@ struct Knobs {
   bool part_small = false;  // PGX_DEBUG part_small
   int narrow_k2 = -1;       // PGX_DEBUG narrow_k2=N
   bool narrow_log = false;  // PGX_DEBUG narrow_log
+  bool dense_body = false;  // PGX_DEBUG densebody: doc-mask filters run the dense row loop, no sparse tile body (A/B)
+  int sparse_k = -1;        // PGX_DEBUG sparsek=N: the sparse body's per-lane row limit (-1: kSparseK) (A/B)
   bool host_profile = false;
 };
 Knobs read_knobs();
@@ -488,6 +492,10 @@ inline NarrowMix narrow_mix(int keybits) {
   m.ic1 = narrow_inverse(m.c1);
   return m;
 }
+
+// Sparse tile body of the query kernels: most selected rows one lane may hold in a sub-step for the wave to walk set
+// bits instead of running the dense row loop (exported as pgx_sparse_k for the tests; PGX_DEBUG sparsek=N overrides)
+constexpr int kSparseK = 4;
 
 struct JitCol {
   int bits = 0;
@@ -544,6 +552,11 @@ struct JitShape {
   int narrow_vbits = 0;
   int narrow_unit = 32;   // records per unit that leaves the scan's rings (ring: two units per bucket)
   bool prefetch2 = false; // raw words of tiles tt+1 AND tt+2 in flight (no gate leaf): twice the bytes in flight
+  // Filters made of doc-mask leaves only (aggregation-only and dense group-by kernels): a sub-step decodes and
+  // aggregates only the rows whose selection bit is set, unless some lane of the wave holds more than sparse_k of them
+  // (then the wave runs the dense row loop for that sub-step).  dense_body: the dense row loop always (A/B, tests)
+  bool dense_body = false;
+  int sparse_k = kSparseK;
 };
 
 // ----- numEntriesScannedInFilter automaton (pgx_stats.cpp builds it, pgx_kernels.hip pgx_fsm_* runs it) -----

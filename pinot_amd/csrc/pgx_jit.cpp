@@ -454,6 +454,7 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
   // clear does not load their words: the row-selective read of the reference's projection
   // (DataFetcher.fetchSingleDictIds over the filtered docIds), at the granularity of a lane's dwords.
   int gate = -1;
+  bool sparse = false;
   {
     bool all_masks = !s.prog_op.empty();
     for (size_t pc = 0; pc < s.prog_op.size() && all_masks; ++pc)
@@ -484,6 +485,17 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
       }
     }
     if (all_masks && impl.size() == 1 && !impl[0].empty() && !compact) gate = impl[0][0];
+    // Sparse tile body: every filter leaf is a doc mask, so a lane holds the selection of its PR rows as one word
+    // before any column is decoded, and only the selected rows are decoded and aggregated (the loop over the word's
+    // set bits in the sub-step below).  Aggregation-only and dense group-by kernels; OP_STATs only at the program's
+    // end (their count is then the selection's, counted by the same ballots).
+    bool has_leaf = false, stat_tail = true;
+    for (size_t pc = 0; pc < s.prog_op.size(); ++pc) {
+      has_leaf |= s.prog_op[pc] == OP_LEAF;
+      if (pc && s.prog_op[pc - 1] == OP_STAT && s.prog_op[pc] != OP_STAT) stat_tail = false;
+    }
+    sparse = all_masks && has_leaf && stat_tail && impl.size() == 1 && !s.dense_body && !emit && !hashm && !compact &&
+             !s.selmask && !s.leafmask;
   }
   auto gate_bits = [&](const std::string& w) {  // the lane's PR bits of gate word w (r0 in scope)
     return s.R == 32 ? w : "((" + w + " >> (r0 & 31)) & " + std::to_string((1u << s.R) - 1u) + "u)";
@@ -658,15 +670,18 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
     e.ln("{");
     e.ind = 5;
     e.ln("const int r0 = rb + ", u * s.R, " * PT + tid * PR;");
-    for (int c = 0; c < ncols; ++c) {
-      if (!s.cols[c].decode) continue;
-      e.ln("u32 v", c, "[PR];");
-      if (s.cols[c].frac)
-        e.ln("pgx_unpack_frac<", s.cols[c].bits, ", PR, ", dwords_per(s, c), ">(&c", c, "[", u * dwords_per(s, c),
-             "], (u32)(((long long)r0 * ", s.cols[c].bits, ") & 31), v", c, ");");
-      else
-        e.ln("pgx_unpack<", s.cols[c].bits, ", PR>(&c", c, "[", u * dwords_per(s, c), "], v", c, ");");
-    }
+    auto emit_unpack = [&]() {  // all PR rows of every decoded column
+      for (int c = 0; c < ncols; ++c) {
+        if (!s.cols[c].decode) continue;
+        e.ln("u32 v", c, "[PR];");
+        if (s.cols[c].frac)
+          e.ln("pgx_unpack_frac<", s.cols[c].bits, ", PR, ", dwords_per(s, c), ">(&c", c, "[", u * dwords_per(s, c),
+               "], (u32)(((long long)r0 * ", s.cols[c].bits, ") & 31), v", c, ");");
+        else
+          e.ln("pgx_unpack<", s.cols[c].bits, ", PR>(&c", c, "[", u * dwords_per(s, c), "], v", c, ");");
+      }
+    };
+    if (!sparse) emit_unpack();
     for (int l = 0; l < nleaves; ++l) {
       if (s.leaf_mode[l] == LEAF_RANGES) e.ln("const u32 W", l, " = pgx_ranges_bits(rg", l, ", nr", l, ", cur", l, ", r0, PR);");
       if (is_docmask(s.leaf_mode[l])) e.ln("const u32 W", l, " = cq", l, "[", u, "] >> (r0 & 31);");
@@ -680,6 +695,34 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
             s.cols[s.agg_col[a]].acc32)
           e.ln("u32 p", a, " = 0u;");
       }
+    if (sparse) {
+      // the lane's selection word: the filter program on the mask words themselves (no per-row booleans); a sub-step
+      // in which some lane holds more than sparse_k selected rows takes the dense row loop (wave-uniform branch)
+      std::vector<std::string> ws;
+      int tmp = 0;
+      for (size_t pc = 0; pc < s.prog_op.size(); ++pc) {
+        const int op = s.prog_op[pc], arg = s.prog_arg[pc];
+        if (op == OP_LEAF) {
+          ws.push_back(std::string(s.leaf_mode[arg] == LEAF_DOCMASK_NOT ? "~W" : "W") + std::to_string(arg));
+        } else if (op == OP_AND || op == OP_OR) {
+          for (int k = 1; k < arg; ++k) {
+            const std::string b = ws.back();
+            ws.pop_back();
+            const std::string a = ws.back();
+            ws.pop_back();
+            const std::string X = "sw" + std::to_string(tmp++);
+            e.ln("const u32 ", X, " = ", a, op == OP_AND ? " & " : " | ", b, ";");
+            ws.push_back(X);
+          }
+        } else if (op == OP_TRUE) {
+          ws.push_back("0xFFFFFFFFu");
+        }
+      }
+      e.ln("u32 sel = ", ws.back(), s.R == 32 ? std::string() : " & " + std::to_string((1u << s.R) - 1u) + "u", ";");
+      e.ln("if (!FULL) sel &= pgx_valid_bits(r0, nd, PR);");
+      e.ln("if (__ballot(__popc(sel) > ", s.sparse_k, ") != 0ull) {");
+      emit_unpack();
+    }
     if (emit) e.ln("u64 recs[PR];");
     if (split) e.ln("u32 msk = 0u;");
     if (s.selmask) e.ln("u32 smk = 0u;");
@@ -907,6 +950,8 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
       e.ind = 6;
       e.ln("}");
     };
+    // aggregation of the row (j, m) in scope
+    auto emit_update = [&]() {
     if (!grouped) {
       for (int a = 0; a < naggs; ++a) {
         const int k = s.agg_kind[a];
@@ -973,10 +1018,55 @@ std::string jit_source(const JitShape& s, int* lds_bytes_out) {
         emit_dense();
       }
     }
+    };
+    emit_update();
     e.ind = 5;
     e.ln("}");
     if (compact) {
       e.ln("  pgx_wave_lds_sync();");
+      e.ln("}");
+    }
+    if (sparse) {
+      // walk the set bits of the wave's selection words: per iteration every lane that still holds one decodes that
+      // row of each column it needs (pgx_unpack_at) and aggregates it; the statistics are scalar popcounts of the
+      // loop's ballots (the same rows the dense loop counts)
+      bool stat = false;
+      for (int op : s.prog_op) stat |= op == OP_STAT;
+      e.ln("} else {");
+      e.ind = 6;
+      e.ln("for (;;) {");
+      e.ind = 7;
+      e.ln("const bool m = sel != 0u;");
+      e.ln("const unsigned long long sb = __ballot(m);");
+      e.ln("if (sb == 0ull) break;");
+      e.ln("wcnt += __popcll(sb);");
+      if (stat) e.ln("st_ent += __popcll(sb);");
+      e.ln("const u32 sj = m ? (u32)__builtin_ctz(sel) : 0u;");
+      e.ln("sel &= sel - 1u;");
+      e.ln("const int j = 0;");
+      std::vector<bool> need(ncols, false);
+      if (grouped)
+        for (int c : s.gcol) need[c] = true;
+      for (int a = 0; a < naggs; ++a)
+        if (s.agg_kind[a] != A_COUNT) need[s.agg_col[a]] = true;
+      for (int c = 0; c < ncols; ++c) {
+        if (!need[c]) continue;
+        const int D = dwords_per(s, c);
+        if (s.cols[c].frac)
+          e.ln("const u32 v", c, "[1] = {pgx_unpack_frac_at<", s.cols[c].bits, ", PR, ", D, ">(&c", c, "[", u * D,
+               "], (u32)(((long long)r0 * ", s.cols[c].bits, ") & 31), sj)};");
+        else
+          e.ln("const u32 v", c, "[1] = {pgx_unpack_at<", s.cols[c].bits, ", PR>(&c", c, "[", u * D, "], sj)};");
+      }
+      for (int c = 0; c < ncols; ++c)
+        if (gcolv[c]) e.ln(s.cols[c].fp ? "double" : "i64", " gv", c, "[1] = {m ? ", s.cols[c].fp ? "dd" : "di", c,
+                           "[v", c, "[0]] : 0};");
+      for (size_t g = 0; g < s.gcol.size(); ++g)
+        if (gremap[g]) e.ln("u32 gr", g, "[1] = {m ? (u32)rm", g, "[v", s.gcol[g], "[0]] : 0u};");
+      emit_update();
+      e.ind = 6;
+      e.ln("}");
+      e.ind = 5;
       e.ln("}");
     }
     if (!grouped)
@@ -1309,6 +1399,8 @@ std::vector<int64_t> shape_key(const JitShape& s, int device) {
   k.push_back(s.part_slab);
   k.push_back(s.dense_pack);
   k.push_back(s.compact);
+  k.push_back(s.dense_body);
+  k.push_back(s.sparse_k);
   k.push_back(s.selmask);
   k.push_back(s.part_narrow);
   k.push_back(s.narrow_vbits);
@@ -1456,6 +1548,9 @@ void* jit_function(const JitShape& s, int device, int* lds_bytes, std::string* e
 }
 
 }  // namespace pgx
+
+// The sparse tile body's per-lane row limit (tests place lanes just below and above it).
+extern "C" int pgx_sparse_k() { return pgx::kSparseK; }
 
 // Debug / build-check entry: compile the kernel source of a shape without a device (declared in include/pgx.h).
 extern "C" int pgx_jit_compile_check(const char* source, char* log, unsigned long log_cap) {
@@ -1652,6 +1747,45 @@ extern "C" int pgx_jit_selftest(int* n_total, char* log, unsigned long log_cap) 
     s.plane_op = {P_ADD_I64, P_ADD_I64};
     s.num_planes = 2;
     s.dense_pack = 40;
+    shapes.push_back(s);
+    s.dense_body = true;  // ... with the dense row loop only (PGX_DEBUG=densebody)
+    shapes.push_back(s);
+    s.dense_body = false;  // two-add form with MIN / MAX planes, a negated second mask leaf ANDed in, a two-column key
+    s.dense_pack = 0;
+    s.leaf_col = {2, -1};
+    s.leaf_mode = {LEAF_DOCMASK_NOT, LEAF_DOCMASK};
+    s.prog_op = {OP_LEAF, OP_LEAF, OP_AND, OP_STAT};
+    s.prog_arg = {1, 0, 2, 0};
+    s.cols[2].decode = true;
+    s.cols[2].bits = 4;
+    s.gcol = {0, 2};
+    s.gmul = {1, 1000};
+    s.dense_slots = 8000;
+    s.group_mode = G_DENSE_GLOBAL;
+    s.agg_kind = {A_COUNT, A_SUM, A_MIN, A_MAX};
+    s.agg_col = {-1, 1, 1, 1};
+    s.plane_op = {P_ADD_I64, P_ADD_I64, P_ADD_I64, P_MIN_ORD, P_MAX_ORD};
+    s.num_planes = 5;
+    shapes.push_back(s);
+    s.group_mode = G_NONE;  // aggregation-only over a negated mask alone, every function; 32 rows per lane (7 bits)
+    s.gcol.clear();
+    s.gmul.clear();
+    s.cols[2].bits = 7;
+    s.cols[2].img = IMG_NONE;
+    s.leaf_col = {2};
+    s.leaf_mode = {LEAF_DOCMASK_NOT};
+    s.prog_op = {OP_LEAF};
+    s.prog_arg = {0};
+    s.agg_kind = {A_COUNT, A_SUM, A_MIN, A_MAX, A_AVG, A_MAX};
+    s.agg_col = {-1, 1, 1, 1, 1, 2};
+    s.plane_op = {P_ADD_I64, P_ADD_I64, P_ADD_I64, P_MIN_ORD, P_MAX_ORD, P_ADD_I64, P_MAX_ORD};
+    s.num_planes = 7;
+    s.R = 32;
+    s.T = 512;
+    shapes.push_back(s);
+    s.R = 8;  // ... eight rows per lane: the 10-bit and the 7-bit column start mid-dword (frac)
+    s.TL = 16;
+    s.cols[0].frac = s.cols[2].frac = true;
     shapes.push_back(s);
   }
   for (int R : {8, 16, 32}) {  // statistics automaton input: every leaf's predicate bits written per lane

@@ -289,6 +289,8 @@ Knobs pgx::read_knobs() {
     else if (o == "nunit=16") k.narrow_unit = 16;
     else if (o == "pf2") k.prefetch2 = true;
     else if (o == "noimg") k.no_img = true;
+    else if (o == "densebody") k.dense_body = true;
+    else if (o.rfind("sparsek=", 0) == 0) k.sparse_k = std::min(32, std::max(0, std::atoi(o.c_str() + 8)));
     else if (o.rfind("head=", 0) == 0) k.lone_head = std::max(2, std::atoi(o.c_str() + 5));
     i = j + 1;
   }
