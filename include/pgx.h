@@ -303,6 +303,12 @@ typedef struct {
 #define PGX_X_THROUGHPUT 0x8u           /* the caller keeps several queries in flight (pgx_execute_async): plan every
                                            segment into one launch per kernel instead of the batched pipeline, whose
                                            early start only shortens a lone query's latency (ABI 6) */
+#define PGX_X_SPARSE_GROUP_SETS 0x10u    /* PGX_DISTINCTCOUNTHLL[MV], PGX_DISTINCTCOUNT[MV] and PGX_PERCENTILE[MV] under
+                                           GROUP BY over a key space that is not dense, is partitioned or has more than
+                                           PGX_HLL_MAX_GROUP_SLOTS slots: their tables get one row per group of the
+                                           result (see PGX_SET_MAX_SPARSE_GROUPS below).  Opt-in: on this route a
+                                           table-size refusal can only come after the scan has run.  Dense key spaces
+                                           of up to PGX_HLL_MAX_GROUP_SLOTS slots run as without the flag. */
 
 /* Execute the query over n segments on the context's device and merge the per-segment partials
  * (the combine).  bindings is [n][num_leaves].  Synchronous w.r.t. the returned result. */
@@ -404,8 +410,19 @@ pgx_status pgx_result_gather(const pgx_result* r, const int64_t* group_index, in
  * single-value one; a multi-value group column or a standard multi-value function (PGX_COUNTMV .. PGX_AVGMV) in the
  * same query; pgx_execute_multi;
  * key domains; a caller's dense table (dense_out, PGX_X_KEEP_DENSE_ON_DEVICE, pgx_query_dense_slots and the other
- * dense-table calls); pgx_execute_timed; PGX_JIT=0. */
+ * dense-table calls); pgx_execute_timed; PGX_JIT=0.
+ * With PGX_X_SPARSE_GROUP_SETS the first of these limits goes: a key space that is not dense (hash keys,
+ * PGX_X_FORCE_HASH) or has more than PGX_HLL_MAX_GROUP_SLOTS slots runs through the global hash table (never the
+ * partitioned record path), and the registers, presence bitmaps and counter tables of all three families are indexed
+ * by the groups the result holds, in the result's order, found per row through a device-side directory from the group
+ * columns' global ids to the group's index.  Same accessors, same contents.  PGX_ERR_UNSUPPORTED on this route, after
+ * the scan: more than PGX_SET_MAX_SPARSE_GROUPS groups; group columns whose global ids take more than 128 bits
+ * (ceil(log2(cardinality)) bits each, at least 1); HLL registers -- 4 bytes x 256 per column and group -- of more than
+ * PGX_HLL_MAX_TABLE_BYTES; the DISTINCTCOUNT and PERCENTILE limits below with the groups in place of the slots.  The
+ * other limits hold as without the flag. */
 #define PGX_HLL_MAX_GROUP_SLOTS 65536
+#define PGX_SET_MAX_SPARSE_GROUPS 131072
+#define PGX_HLL_MAX_TABLE_BYTES (256u << 20)
 pgx_status pgx_result_hll(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
                           uint8_t* registers);
 /* Host only, no device needed: codes[i] = (register << 8) | rank of offer((int) hashCode(value i)), the per-dictId
@@ -436,8 +453,8 @@ pgx_status pgx_hll_codes(int32_t data_type, const void* values, const int32_t* s
  * staged segment has compiles, and the execution checks its own segments ("DISTINCTCOUNT on multi-value column",
  * "multi-value function on single-value column").
  * PGX_ERR_UNSUPPORTED (the caller falls back): every limit of the HLL forms above, and presence bitmaps -- one bit per
- * dictId, per group slot and per distinct dictionary of the executed segments -- of more than
- * PGX_DISTINCT_MAX_TABLE_BYTES in all. */
+ * dictId, per group slot (with PGX_X_SPARSE_GROUP_SETS: per group of the result) and per distinct dictionary of the
+ * executed segments -- of more than PGX_DISTINCT_MAX_TABLE_BYTES in all. */
 #define PGX_DISTINCT_MAX_TABLE_BYTES (256u << 20)
 pgx_status pgx_result_distinct_counts(const pgx_result* r, int32_t agg_index, int64_t first_group, int64_t num_groups,
                                       int64_t* counts);
@@ -472,8 +489,9 @@ pgx_status pgx_java_hash_codes(int32_t data_type, const void* values, const int3
  * holds the column holds it single-value, and for PGX_PERCENTILE when every one holds it multi-value; a column no
  * staged segment has compiles, and the execution checks its own segments.
  * PGX_ERR_UNSUPPORTED (the caller falls back): every limit of the HLL forms above; a STRING column (the reference's
- * executor cannot hand one to these functions); and counter tables -- 8 bytes per dictId, per group slot and per
- * distinct dictionary of the executed segments -- of more than PGX_PERCENTILE_MAX_TABLE_BYTES in all. */
+ * executor cannot hand one to these functions); and counter tables -- 8 bytes per dictId, per group slot (with
+ * PGX_X_SPARSE_GROUP_SETS: per group of the result) and per distinct dictionary of the executed segments -- of more
+ * than PGX_PERCENTILE_MAX_TABLE_BYTES in all. */
 #define PGX_PERCENTILE_MAX_TABLE_BYTES (256u << 20)
 pgx_status pgx_result_percentile_counts(const pgx_result* r, int32_t agg_index, int64_t first_group,
                                         int64_t num_groups, int64_t* counts);

@@ -62,9 +62,11 @@ void distinct_mark(pgx_ctx* ctx, const SelScan& S, DistinctRun& D) {
     }
   D.items.upload(ctx, S.st, "DISTINCTCOUNT items H2D", "DISTINCTCOUNTMV items H2D");
   D.items.launch_sv(S, "pgx_distinct_mark", pgx_launch_distinct_mark, "DISTINCTCOUNT marks",
-                    "pgx_distinct_mark_group", pgx_launch_distinct_mark_group, "DISTINCTCOUNT group marks");
+                    "pgx_distinct_mark_group", pgx_launch_distinct_mark_group, "DISTINCTCOUNT group marks",
+                    "pgx_distinct_mark_group_sparse", pgx_launch_distinct_mark_group_sparse);
   D.items.launch_mv(S, "pgx_distinct_mark_mv", pgx_launch_distinct_mark_mv, "DISTINCTCOUNTMV marks",
-                    "pgx_distinct_mark_mv_group", pgx_launch_distinct_mark_mv_group, "DISTINCTCOUNTMV group marks");
+                    "pgx_distinct_mark_mv_group", pgx_launch_distinct_mark_mv_group, "DISTINCTCOUNTMV group marks",
+                    "pgx_distinct_mark_mv_group_sparse", pgx_launch_distinct_mark_mv_group_sparse);
 }
 
 // The result's groups: per bitmap the rows' sizes (pgx_distinct_count), then exactly that many hash codes
@@ -77,6 +79,7 @@ void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& 
   R->dist_start.assign(nd, std::vector<int64_t>(groups + 1, 0));
   R->dist_codes.assign(nd, {});
   if (nd == 0 || groups == 0) return;
+  sel_result_rows_ok(rows, slots);
   const int budget = 8 * std::max(1, ctx->num_cus);
   const int wgs = int(std::min<size_t>(groups, size_t(budget)));
   DevBuf rdev(ctx, groups * 8);
@@ -95,10 +98,12 @@ void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& 
       p.m = &m;
       p.cdev = DevBuf(ctx, groups * 4);
       p.counts.assign(groups, 0);
-      PGX_LAUNCH(st, "pgx_distinct_count",
-                 pgx_launch_distinct_count(m.table.as<uint32_t>(), m.col->card, rdev.as<int64_t>(), int64_t(groups),
-                                           int64_t(slots), p.cdev.as<uint32_t>(), wgs, st),
-                 "DISTINCTCOUNT sizes");
+      sel_result_stretches(groups, slots, [&](size_t c0, size_t cn, uint64_t cs) {
+        PGX_LAUNCH(st, "pgx_distinct_count",
+                   pgx_launch_distinct_count(m.table.as<uint32_t>() + c0 * m.words, m.col->card, rdev.as<int64_t>(),
+                                             int64_t(cn), int64_t(cs), p.cdev.as<uint32_t>() + c0, wgs, st),
+                   "DISTINCTCOUNT sizes");
+      });
       hip_check(hipMemcpyAsync(p.counts.data(), p.cdev.p, groups * 4, hipMemcpyDeviceToHost, st),
                 "DISTINCTCOUNT sizes D2H");
       parts[k].push_back(std::move(p));
@@ -117,11 +122,13 @@ void distinct_collect(pgx_ctx* ctx, DistinctRun& D, const std::vector<int64_t>& 
       p.codes.assign(size_t(total), 0);
       hip_check(hipMemcpyAsync(p.odev.p, p.off.data(), groups * 8, hipMemcpyHostToDevice, st),
                 "DISTINCTCOUNT offsets H2D");
-      PGX_LAUNCH(st, "pgx_distinct_emit",
-                 pgx_launch_distinct_emit(p.m->table.as<uint32_t>(), p.m->col->card, rdev.as<int64_t>(),
-                                          p.odev.as<int64_t>(), int64_t(groups), int64_t(slots), p.m->hash,
-                                          p.out.as<int32_t>(), total, per_row, wgs, st),
-                 "DISTINCTCOUNT hash codes");
+      sel_result_stretches(groups, slots, [&](size_t c0, size_t cn, uint64_t cs) {
+        PGX_LAUNCH(st, "pgx_distinct_emit",
+                   pgx_launch_distinct_emit(p.m->table.as<uint32_t>() + c0 * p.m->words, p.m->col->card,
+                                            rdev.as<int64_t>(), p.odev.as<int64_t>() + c0, int64_t(cn), int64_t(cs),
+                                            p.m->hash, p.out.as<int32_t>(), total, per_row, wgs, st),
+                   "DISTINCTCOUNT hash codes");
+      });
       hip_check(hipMemcpyAsync(p.codes.data(), p.out.p, size_t(total) * 4, hipMemcpyDeviceToHost, st),
                 "DISTINCTCOUNT hash codes D2H");
     }

@@ -109,24 +109,28 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark(const DistinctIte
 // Rows J0 .. J0 + 15 of a mask word whose dictIds are decoded (v): slots, bitmap words, atomics.  Half a word at a
 // time: 16 loads in flight per lane and pass.  The word's rows all lie inside the group columns' padded indexes, so the
 // id loads are unconditional; a row that marks nothing takes remap entry 0 and reads word 0 of the table.
-template <int J0>
-__device__ __forceinline__ void dist_group_rows(const DistinctGroupItem& G, const HllGroupKey& K, uint32_t sel,
-                                                int32_t d0, uint32_t (&v)[32]) {
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+template <int J0, class Key>
+__device__ __forceinline__ void dist_group_rows(const DistinctGroupItem& G, const Key& K, uint32_t sel, int32_t d0,
+                                                uint32_t (&v)[32]) {
+  const uint32_t slots32 = sel_key_rows(K);  // <= kHllMaxGroupSlots, sparse: <= kSelMaxSparseGroups (launcher)
   const uint32_t bw = dist_bitmap_words(G.d.card);
   uint32_t s[16];
-  for (int g = 0; g < K.ngcols; ++g) {
-    const uint32_t* __restrict__ gf = G.g[g].fwd;
-    const int32_t* __restrict__ rm = G.g[g].remap;
-    const int gb = G.g[g].bits;
-    const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+  if constexpr (std::is_same<Key, HllGroupKey>::value) {
+    for (int g = 0; g < K.ngcols; ++g) {
+      const uint32_t* __restrict__ gf = G.g[g].fwd;
+      const int32_t* __restrict__ rm = G.g[g].remap;
+      const int gb = G.g[g].bits;
+      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t on = 0u - ((sel >> (J0 + j)) & 1u);
-      const uint32_t id = pgx_fwd_value2(gf, d0 + J0 + j, gb) & on;
-      const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
-      s[j] = hll_mv_fold(g == 0 ? 0u : s[j], gid, mul);
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t on = 0u - ((sel >> (J0 + j)) & 1u);
+        const uint32_t id = pgx_fwd_value2(gf, d0 + J0 + j, gb) & on;
+        const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
+        s[j] = hll_mv_fold(g == 0 ? 0u : s[j], gid, mul);
+      }
     }
+  } else {
+    sel_word_slots<J0>(G.g, K, sel, d0, s);
   }
   uint32_t* const table = G.d.out;
 #pragma unroll
@@ -144,13 +148,15 @@ __device__ __forceinline__ void dist_group_rows(const DistinctGroupItem& G, cons
       atomicOr(&table[static_cast<size_t>(s[j]) * bw + (v[J0 + j] >> 5)], 1u << (v[J0 + j] & 31u));
 }
 
+// Key: HllGroupKey or SelSparseKey (pgx_hll_offer_group); only the slot computation differs.
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_group(const DistinctGroupItem* __restrict__ items,
-                                                                     int nitems, const HllGroupKey K) {
+                                                                     int nitems, const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   const DistinctGroupItem& G = items[item];
   const DistinctItem A = G.d;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);
+  const uint32_t slots32 = sel_key_rows(K);
   const uint32_t bw = dist_bitmap_words(A.card);
   sel_walk(
       A, sel_gcols_ok(G.g, K) ? sel_words(A) : 0,
@@ -225,8 +231,9 @@ __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_mv(const Distinct
 }
 
 // The same into the slots' rows in HBM: every value of a doc into the row of the doc's slot (sel_mv_group_walk).
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_distinct_mark_mv_group(const DistinctMvGroupItem* __restrict__ items,
-                                                                        int nitems, const HllGroupKey K) {
+                                                                        int nitems, const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t slot_of[32 * kHllBlock];
@@ -344,9 +351,21 @@ extern "C" hipError_t pgx_launch_distinct_mark_group(const pgx::DistinctGroupIte
                                                      hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_distinct_mark_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_distinct_mark_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::DistinctGroupItem& g) { return dist_item_ok(g.d) && pgx::sel_gcols_host_ok(g.g, ngcols); },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+// The sparse forms: every item's `out` holds key->groups rows; key: the caller's host struct (pgx_hll.hip).
+extern "C" hipError_t pgx_launch_distinct_mark_group_sparse(const pgx::DistinctGroupItem* items,
+                                                            const pgx::DistinctGroupItem* check, int nitems,
+                                                            const pgx::SelSparseKey* key, int wgs_per_item,
+                                                            hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_distinct_mark_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::DistinctGroupItem& g) { return dist_item_ok(g.d) && pgx::sel_gcols_host_ok(g.g, ngcols); }, *key);
 }
 
 // The start arrays are device data, so the kernels clamp every value range to `total`.
@@ -363,11 +382,25 @@ extern "C" hipError_t pgx_launch_distinct_mark_mv_group(const pgx::DistinctMvGro
                                                         hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_distinct_mark_mv_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_distinct_mark_mv_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::DistinctMvGroupItem& m) {
         return dist_item_ok(m.g.d) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
       },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+extern "C" hipError_t pgx_launch_distinct_mark_mv_group_sparse(const pgx::DistinctMvGroupItem* items,
+                                                               const pgx::DistinctMvGroupItem* check, int nitems,
+                                                               const pgx::SelSparseKey* key, int wgs_per_item,
+                                                               hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_distinct_mark_mv_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::DistinctMvGroupItem& m) {
+        return dist_item_ok(m.g.d) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
+      },
+      *key);
 }
 
 // table: slots rows of (card + 31) / 32 words; rows: nrows row indexes (int64, device); counts: nrows u32 (device).

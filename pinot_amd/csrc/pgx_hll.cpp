@@ -7,8 +7,11 @@
 // are in pgx_hll.hip.  Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
 #include "pgx_hash.h"
 #include "pgx_host.h"
+#include "pgx_sel_key.h"
 
 namespace pgxh {
+
+static_assert(kSelKeyMaxCols == pgx::kMaxGroupCols, "pgx_sel_key.h lays out one field per group column");
 
 // MurmurHash.hashLong (stream-lib 2.7.0: MurmurHash2 over the low, then the high half), in Java int arithmetic.
 static uint32_t murmur_hash_long(int64_t v) {
@@ -105,6 +108,21 @@ static void sel_group_columns(pgx_ctx* ctx, SelScan& S) {
     }
 }
 
+// group i's global id in group column g, from the result's key (a segment and its dictId)
+static int64_t group_global_id(const GlobalDict& gd, int n, int32_t seg, int32_t id) {
+  if (seg < 0 || seg >= n) fail(PGX_ERR_INTERNAL, "group key without a segment");
+  const std::vector<int32_t>* rm = gd.identity ? nullptr : gd.remap[size_t(seg)].get();
+  return rm ? (*rm)[size_t(id)] : id;
+}
+
+// The directory of a sparse run: the result's groups' packed keys in an open-addressing table of at least twice as many
+// slots (pgx_sel_dir_build), and the key the sparse group launches take.
+struct SelDirectory {
+  DevBuf keys, tkey, tstate, tidx, miss;
+  std::vector<unsigned long long> host;  // the packed keys, W words each (alive until the stream was waited for)
+  pgx::SelSparseKey key{};
+};
+
 // A query with DISTINCTCOUNTHLL / DISTINCTCOUNTHLLMV functions: the rest of it (its filter, its standard functions or
 // COUNT(*) alone, its GROUP BY) runs through the query kernels, which also write every scanned row's selection bit;
 // pgx_hll_offer[_group] then offers every selected row's code, pgx_hll_offer_mv[_group] the code of every value of
@@ -113,6 +131,10 @@ static void sel_group_columns(pgx_ctx* ctx, SelScan& S) {
 // stream and collects the result's sets afterwards; PERCENTILE and PERCENTILEMV (codes 15, 14) are the third family:
 // pgx_percentile.cpp counts the selected values per dictId and collects the groups' (value, count) pairs.  Planned
 // afresh every time (no plan cache).
+// With PGX_X_SPARSE_GROUP_SETS a GROUP BY whose key space is not dense or has more than PGX_HLL_MAX_GROUP_SLOTS slots
+// takes the sparse route: the scan runs first (through the global hash table, never the partitioned record path: the
+// selection bits must be those of one complete scan by kernels known to write them), the result's groups go into a
+// directory (SelDirectory), and the three families' tables get one row per group, in the result's order.
 void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
              const pgx_exec_opts* opts, pgx_result* R, hipStream_t st, const Domain* dom) {
   const uint32_t xflags = opts ? opts->flags : 0;
@@ -173,16 +195,24 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   const size_t nh = hcols.size();
 
   // 1. the rest of the query, with selection bits
+  const bool may_sparse = ng > 0 && (xflags & PGX_X_SPARSE_GROUP_SETS) != 0;
   ExecPlan P;
   P.want_selmask = true;
-  plan_query(ctx, qs, segs, n, bindings, xflags, P);
+  plan_query(ctx, qs, segs, n, bindings, may_sparse ? xflags | PGX_X_NO_PARTITION : xflags, P);
   const KQuery& K = P.kq;
   const bool dense = K.group_mode == G_DENSE_LDS || K.group_mode == G_DENSE_GLOBAL;
-  if (ng > 0 && (!dense || P.use_part || P.dense_slots > uint64_t(PGX_HLL_MAX_GROUP_SLOTS)))
+  const bool sparse = ng > 0 && (!dense || P.use_part || P.dense_slots > uint64_t(PGX_HLL_MAX_GROUP_SLOTS));
+  if (sparse && (!may_sparse || P.use_part))
     fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: dense key spaces of up to PGX_HLL_MAX_GROUP_SLOTS only");
-  const uint64_t slots = ng > 0 ? P.dense_slots : 1;
-  distinct_plan(ctx, segs, n, slots, D);  // (refuses tables over PGX_DISTINCT_MAX_TABLE_BYTES before anything runs)
-  percentile_plan(ctx, segs, n, slots, Q);  // (... over PGX_PERCENTILE_MAX_TABLE_BYTES, and STRING columns)
+  uint64_t slots = ng > 0 && !sparse ? P.dense_slots : 1;  // (a sparse run: the result's groups, known after the scan)
+  if (!sparse) {
+    distinct_plan(ctx, segs, n, slots, D);  // (refuses tables over PGX_DISTINCT_MAX_TABLE_BYTES before anything runs)
+    percentile_plan(ctx, segs, n, slots, Q);  // (... over PGX_PERCENTILE_MAX_TABLE_BYTES, and STRING columns)
+  } else {
+    for (const auto& c : Q.cols)  // (the one refusal of percentile_plan that does not depend on the groups)
+      for (int s = 0; s < n; ++s)
+        if (segs[s]->col(c).data_type == PGX_STRING) fail(PGX_ERR_UNSUPPORTED, "PERCENTILE on STRING column " + c);
+  }
   P.sel_off.assign(size_t(n), 0);
   int64_t words = 0;
   int max_words = 0;
@@ -201,46 +231,152 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   if (!scanned)  // every segment empty: nothing scanned, registers stay zero
     for (int s = 0; s < n; ++s)
       if (P.ksegs[size_t(s)].num_docs != 0) fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL needs the query kernels");
-  alloc_outputs(ctx, P, B, nullptr, 0);
-  reset_outputs(P, B, st);
-  launch_scan(P, st);
+  const bool hash = hash_mode(K.group_mode);  // (a sparse run only)
+  uint64_t hash_est = 0;
+  if (hash) {  // the table's first size and its growth: run_query's
+    P.hash_cap = hash_est = initial_hash_cap(segs, n, P);
+    if (scanned) P.hash_cap = std::min<uint64_t>(P.hash_cap, std::max<uint64_t>(uint64_t(1) << 20, q.hash_cap_hint.load()));
+  }
+  for (int attempt = 0; attempt < 6; ++attempt) {
+    // A pass that overflowed the hash table is run again whole.  The generated kernels write the selection words with
+    // plain stores, a word per lane of every tile they visit; the words are cleared again all the same, so that the
+    // bits the functions read are those of the one complete pass whatever an abandoned one left behind.
+    if (attempt)
+      hip_check(hipMemsetAsync(P.sel_buf.p, 0, size_t(std::max<int64_t>(words, 1)) * 4, st), "selection masks");
+    alloc_outputs(ctx, P, B, nullptr, 0);
+    reset_outputs(P, B, st);
+    launch_scan(P, st);
+    if (!hash) break;
+    unsigned long long* outs = reinterpret_cast<unsigned long long*>(B.host.bytes() + B.off_outs);
+    hip_check(hipMemcpyAsync(outs, B.dev() + B.off_outs, kOutsBytes, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    if (outs[24] == 0) break;
+    if (attempt == 5) fail(PGX_ERR_OOM, "group-by hash table overflow");
+    P.hash_cap = std::max(P.hash_cap * 4, hash_est);  // table full: grow and rerun
+  }
+  if (hash && P.hash_cap > q.hash_cap_hint.load()) q.hash_cap_hint.store(P.hash_cap);
 
-  // 2. the offers, on the same stream: one item per (HLL column, segment)
-  DevBuf regs(ctx, std::max<size_t>(1, nh * slots * kHllRegs * 4));
-  if (nh) hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
-  SelScan S;
-  S.q = &q;
-  S.P = &P;
-  S.segs = segs;
-  S.n = n;
-  S.ng = ng;
-  S.slots = slots;
-  S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size() + Q.cols.size()) * size_t(n));
-  S.scanned = scanned;
-  S.st = st;
-  sel_group_columns(ctx, S);
-  HllItems H;
-  for (size_t k = 0; k < nh; ++k)
-    for (int s = 0; s < n; ++s) {
-      const StagedColumn& col = segs[s]->col(hcols[k]);
-      HllItem h{};
-      h.codes = hll_code_table(ctx, col);
-      h.out = regs.as<uint32_t>() + k * slots * kHllRegs;
-      h.ncodes = col.card;
-      H.add(S, s, col, hmv[k], "DISTINCTCOUNTHLL", h);
-    }
-  H.upload(ctx, st, "HLL items H2D", "HLL MV items H2D");
-  // the multi-value and the single-value items: one launch each, on the same stream, into their own register blocks
-  H.launch_mv(S, "pgx_hll_offer_mv", pgx_launch_hll_offer_mv, "HLL MV offers", "pgx_hll_offer_mv_group",
-              pgx_launch_hll_offer_mv_group, "HLL MV group offers");
-  H.launch_sv(S, "pgx_hll_offer", pgx_launch_hll_offer, "HLL offers", "pgx_hll_offer_group",
-              pgx_launch_hll_offer_group, "HLL group offers");
-  // the DISTINCTCOUNT[MV] marks, on the same stream
-  if (!D.cols.empty()) distinct_mark(ctx, S, D);
-  // the PERCENTILE[MV] counts, likewise
-  if (!Q.cols.empty()) percentile_count(ctx, S, Q);
+  // 2. the offers, on the same stream: one item per (HLL column, segment).  A sparse run needs the result's groups
+  // first: finish_result waits for the stream and yields every group (a trim is a call of its own, on the result).
   pgx_result Rs;
-  finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
+  SelDirectory dir;
+  bool offer = true;
+  if (sparse) {
+    finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);
+    if (Rs.lazy) fail(PGX_ERR_INTERNAL, "device-resident groups on the sparse route");  // (never planned: NO_PARTITION)
+    const int64_t groups = Rs.num_groups;
+    if (groups > int64_t(PGX_SET_MAX_SPARSE_GROUPS))
+      fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: more than PGX_SET_MAX_SPARSE_GROUPS groups");
+    std::vector<int64_t> cards(size_t(ng), 0);
+    for (int g = 0; g < ng; ++g) cards[size_t(g)] = P.gdicts[size_t(g)].card;
+    SelKeyLayout L;
+    if (!sel_key_layout(cards.data(), ng, L))
+      fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: group keys of more than 128 bits");
+    if (uint64_t(nh) * uint64_t(groups) * kHllRegs * 4 > uint64_t(PGX_HLL_MAX_TABLE_BYTES))
+      fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL: registers over PGX_HLL_MAX_TABLE_BYTES");
+    offer = groups > 0;
+    if (offer) {
+      slots = uint64_t(groups);
+      distinct_plan(ctx, segs, n, slots, D);    // (the byte limits, at one row per group)
+      percentile_plan(ctx, segs, n, slots, Q);
+      // the groups' keys.  One-word keys claim their slot on the key itself and ~0 is the empty slot: a result that
+      // holds that key (every field all ones, 64 bits in all) takes two words, where a state word claims the slot
+      dir.host.assign(size_t(groups) * 2, 0);
+      std::vector<int64_t> gids(size_t(ng), 0);
+      bool all_ones = false;
+      for (int64_t i = 0; i < groups; ++i) {
+        for (int g = 0; g < ng; ++g)
+          gids[size_t(g)] = group_global_id(P.gdicts[size_t(g)], n, Rs.key_seg[size_t(g)][size_t(i)],
+                                            Rs.key_id[size_t(g)][size_t(i)]);
+        uint64_t k[2];
+        if (!sel_key_pack(L, gids.data(), k)) fail(PGX_ERR_INTERNAL, "group id outside its dictionary");
+        dir.host[size_t(i) * 2] = k[0];
+        dir.host[size_t(i) * 2 + 1] = k[1];
+        all_ones = all_ones || k[0] == ~0ull;
+      }
+      const int W = L.W == 1 && !all_ones ? 1 : 2;
+      if (W == 1) {
+        for (int64_t i = 0; i < groups; ++i) dir.host[size_t(i)] = dir.host[size_t(i) * 2];
+        dir.host.resize(size_t(groups));
+      }
+      uint64_t cap = 2;
+      while (cap < 2 * uint64_t(groups)) cap *= 2;
+      dir.keys = DevBuf(ctx, dir.host.size() * 8);
+      dir.tkey = DevBuf(ctx, cap * uint64_t(W) * 8);
+      dir.tstate = DevBuf(ctx, cap * 4);
+      dir.tidx = DevBuf(ctx, cap * 4);
+      dir.miss = DevBuf(ctx, 8);
+      hip_check(hipMemcpyAsync(dir.keys.p, dir.host.data(), dir.host.size() * 8, hipMemcpyHostToDevice, st),
+                "group directory keys H2D");
+      hip_check(hipMemsetAsync(dir.miss.p, 0, 8, st), "group directory misses");
+      PGX_LAUNCH(st, "pgx_sel_dir_build",
+                 pgx_launch_sel_dir_build(dir.keys.as<unsigned long long>(), dir.host.data(), groups, W,
+                                          dir.tkey.as<unsigned long long>(), dir.tstate.as<unsigned int>(),
+                                          dir.tidx.as<uint32_t>(), cap, st),
+                 "group directory build");
+      pgx::SelSparseKey& SK = dir.key;
+      SK.keys = dir.tkey.as<unsigned long long>();
+      SK.state = dir.tstate.as<unsigned int>();
+      SK.index = dir.tidx.as<uint32_t>();
+      SK.miss = dir.miss.as<unsigned long long>();
+      SK.cap = cap;
+      for (int g = 0; g < ng; ++g) {
+        SK.shift[g] = L.shift[g];
+        SK.word[g] = L.word[g];
+        SK.bits[g] = L.bits[g];
+      }
+      SK.groups = uint32_t(groups);
+      SK.W = W;
+      SK.ngcols = ng;
+    }
+  }
+  DevBuf regs(ctx, std::max<size_t>(1, nh * slots * kHllRegs * 4));
+  SelScan S;
+  HllItems H;
+  if (offer) {
+    if (nh) hip_check(hipMemsetAsync(regs.p, 0, nh * slots * kHllRegs * 4, st), "HLL registers");
+    S.q = &q;
+    S.P = &P;
+    S.segs = segs;
+    S.n = n;
+    S.ng = ng;
+    S.slots = slots;
+    S.sparse = sparse ? &dir.key : nullptr;
+    S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size() + Q.cols.size()) * size_t(n));
+    S.scanned = scanned;
+    S.st = st;
+    sel_group_columns(ctx, S);
+    for (size_t k = 0; k < nh; ++k)
+      for (int s = 0; s < n; ++s) {
+        const StagedColumn& col = segs[s]->col(hcols[k]);
+        HllItem h{};
+        h.codes = hll_code_table(ctx, col);
+        h.out = regs.as<uint32_t>() + k * slots * kHllRegs;
+        h.ncodes = col.card;
+        H.add(S, s, col, hmv[k], "DISTINCTCOUNTHLL", h);
+      }
+    H.upload(ctx, st, "HLL items H2D", "HLL MV items H2D");
+    // the multi-value and the single-value items: one launch each, on the same stream, into their own register blocks
+    H.launch_mv(S, "pgx_hll_offer_mv", pgx_launch_hll_offer_mv, "HLL MV offers", "pgx_hll_offer_mv_group",
+                pgx_launch_hll_offer_mv_group, "HLL MV group offers", "pgx_hll_offer_mv_group_sparse",
+                pgx_launch_hll_offer_mv_group_sparse);
+    H.launch_sv(S, "pgx_hll_offer", pgx_launch_hll_offer, "HLL offers", "pgx_hll_offer_group",
+                pgx_launch_hll_offer_group, "HLL group offers", "pgx_hll_offer_group_sparse",
+                pgx_launch_hll_offer_group_sparse);
+    // the DISTINCTCOUNT[MV] marks, on the same stream
+    if (!D.cols.empty()) distinct_mark(ctx, S, D);
+    // the PERCENTILE[MV] counts, likewise
+    if (!Q.cols.empty()) percentile_count(ctx, S, Q);
+  }
+  if (!sparse) {
+    finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream (the items' host copies included)
+  } else if (offer) {
+    // every selected row's group is in the result: a row the directory did not find is a fault of this library
+    unsigned long long missed = 0;
+    hip_check(hipMemcpyAsync(&missed, dir.miss.p, 8, hipMemcpyDeviceToHost, st), "group directory misses D2H");
+    hip_check(hipStreamSynchronize(st), "sync");  // (the items' and the keys' host copies included)
+    if (missed != 0) fail(PGX_ERR_INTERNAL, "selected rows whose group the result does not hold");
+  }
 
   // 3. assemble in the request's order; numEntriesScannedPostFilter counts each HLL column among the projected ones
   int extra = 0;  // (a column that functions of several families name counts once)
@@ -300,30 +436,33 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     percentile_collect(ctx, Q, std::vector<int64_t>(), slots, st, R);
     return;
   }
-  // registers of the groups the result holds: their slots from the keys (global id x gmul), narrowed on the device
+  // registers of the groups the result holds: their slots from the keys (global id x gmul; a sparse run: the group's
+  // index), narrowed on the device
   std::vector<int64_t> gslot(size_t(groups), 0);
-  for (int g = 0; g < ng; ++g) {
+  if (sparse) std::iota(gslot.begin(), gslot.end(), int64_t(0));
+  for (int g = 0; g < ng && !sparse; ++g) {
     const GlobalDict& gd = P.gdicts[size_t(g)];
-    for (int64_t i = 0; i < groups; ++i) {
-      const int32_t s = R->key_seg[size_t(g)][size_t(i)], id = R->key_id[size_t(g)][size_t(i)];
-      if (s < 0 || s >= n) fail(PGX_ERR_INTERNAL, "group key without a segment");
-      const std::vector<int32_t>* rm = gd.identity ? nullptr : gd.remap[size_t(s)].get();
-      const int64_t gid = rm ? (*rm)[size_t(id)] : id;
-      gslot[size_t(i)] += gid * int64_t(K.gmul[g]);
-    }
+    for (int64_t i = 0; i < groups; ++i)
+      gslot[size_t(i)] += group_global_id(gd, n, R->key_seg[size_t(g)][size_t(i)], R->key_id[size_t(g)][size_t(i)]) *
+                          int64_t(K.gmul[g]);
   }
   for (int64_t i = 0; i < groups; ++i)
     if (gslot[size_t(i)] < 0 || uint64_t(gslot[size_t(i)]) >= slots) fail(PGX_ERR_INTERNAL, "group slot out of range");
   distinct_collect(ctx, D, gslot, slots, st, R);
   percentile_collect(ctx, Q, gslot, slots, st, R);
   if (nh == 0) return;
+  // (a sparse run of more than 65,536 groups goes through pgx_hll_narrow in stretches, each a table of its own read
+  // with the first entries of sdev: that rests on gslot[i] == i, checked here as the other two collectors check it)
+  sel_result_rows_ok(gslot, slots);
   DevBuf sdev(ctx, size_t(groups) * 8), odev(ctx, size_t(groups) * kHllRegs);
   hip_check(hipMemcpyAsync(sdev.p, gslot.data(), size_t(groups) * 8, hipMemcpyHostToDevice, st), "HLL slots H2D");
   for (size_t k = 0; k < nh; ++k) {
-    PGX_LAUNCH(st, "pgx_hll_narrow",
-               pgx_launch_hll_narrow(regs.as<uint32_t>() + k * slots * kHllRegs, sdev.as<int64_t>(), groups,
-                                     int64_t(slots), odev.as<uint32_t>(), st),
-               "HLL narrow");
+    sel_result_stretches(size_t(groups), slots, [&](size_t c0, size_t cn, uint64_t cs) {
+      PGX_LAUNCH(st, "pgx_hll_narrow",
+                 pgx_launch_hll_narrow(regs.as<uint32_t>() + (k * slots + c0) * kHllRegs, sdev.as<int64_t>(), int64_t(cn),
+                                       int64_t(cs), odev.as<uint32_t>() + c0 * (kHllRegs / 4), st),
+                 "HLL narrow");
+    });
     hip_check(hipMemcpyAsync(R->hll_regs.data() + k * size_t(groups) * kHllRegs, odev.p, size_t(groups) * kHllRegs,
                              hipMemcpyDeviceToHost, st),
               "HLL registers D2H");

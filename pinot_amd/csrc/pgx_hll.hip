@@ -132,13 +132,42 @@ __device__ __forceinline__ void hll_group_rows(const HllGroupItem& G, const HllG
     if (v[j] != 0u) atomicMax(&table[static_cast<size_t>(v[j] >> 16) * kHllRegs + ((v[j] >> 8) & 0xFFu)], v[j] & 0xFFu);
 }
 
+// The same through a sparse run's directory.  A group's index takes 17 bits, so it does not share the word with the
+// code: the 16 rows' indexes are looked up first (sel_word_slots: only rows that still offer), then the registers and
+// the few atomics as above.  A row whose key the directory does not hold offers nothing.
+template <int J0>
+__device__ __forceinline__ void hll_group_rows(const HllGroupItem& G, const SelSparseKey& K, int32_t d0,
+                                               uint32_t (&v)[32]) {
+  uint32_t on16 = 0u;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) on16 |= static_cast<uint32_t>((v[J0 + j] & 0xFFFFu) != 0u) << (J0 + j);
+  uint32_t s[16];
+  sel_word_slots<J0>(G.g, K, on16, d0, s);
+  uint32_t* const table = G.h.out;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const bool ok = s[j] < K.groups;
+    s[j] = ok ? s[j] : 0u;
+    const uint32_t c = ok ? v[J0 + j] & 0xFFFFu : 0u;
+    const uint32_t cur = table[static_cast<size_t>(s[j]) * kHllRegs + (c >> 8)];
+    v[J0 + j] = cur < (c & 0xFFu) ? c : 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    if (v[J0 + j] != 0u)
+      atomicMax(&table[static_cast<size_t>(s[j]) * kHllRegs + (v[J0 + j] >> 8)], v[J0 + j] & 0xFFu);
+}
+
+// Key: HllGroupKey (a dense key space: the slot is a multiply-add) or SelSparseKey (the result's groups: the slot is a
+// directory lookup); only the slot computation differs.
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_group(const HllGroupItem* __restrict__ items, int nitems,
-                                                                 const HllGroupKey K) {
+                                                                 const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   const HllGroupItem& G = items[item];
   const HllItem A = G.h;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  const uint32_t slots32 = sel_key_rows(K);  // <= kHllMaxGroupSlots, sparse: <= kSelMaxSparseGroups (launcher)
   sel_walk(
       A, sel_gcols_ok(G.g, K) ? sel_words(A) : 0,
       [&](int64_t w, uint32_t sel) PGX_SEL_OP {
@@ -207,8 +236,9 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv(const HllMvItem* _
 }
 
 // The same over a table of slots x 256 registers in HBM: every value of a doc into the doc's slot (sel_mv_group_walk).
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_hll_offer_mv_group(const HllMvGroupItem* __restrict__ items,
-                                                                    int nitems, const HllGroupKey K) {
+                                                                    int nitems, const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t slot_of[32 * kHllBlock];
@@ -236,7 +266,69 @@ __global__ void __launch_bounds__(kHllBlock) pgx_hll_narrow(const uint32_t* __re
   out[idx] = packed;
 }
 
+// ---- the group directory of a sparse run (SelSparseKey, pgx_internal.h) -----------------------------------------------
+// Thread i puts key i (W words) into the open-addressing table with value i, on the pattern of pgx_join_build
+// (pgx_merge.hip): pgx_insert over the whole table -- the keys are distinct and cap >= n, so a free slot always exists.
+__global__ void __launch_bounds__(kHllBlock) pgx_sel_dir_build(const unsigned long long* __restrict__ keys, int64_t n,
+                                                               int W, unsigned long long* __restrict__ tkey,
+                                                               unsigned int* __restrict__ tstate,
+                                                               uint32_t* __restrict__ tidx, uint64_t cap) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t h = W == 1 ? pgx_insert<1>(tkey, tstate, cap, {keys[i]}, cap)
+                           : pgx_insert<2>(tkey, tstate, cap, {keys[2 * i], keys[2 * i + 1]}, cap);
+  if (h >= 0) tidx[h] = static_cast<uint32_t>(i);
+}
+
+// out[i] = the group of key i (W words), or kHllNoSlot (counted in *K.miss): the lookup every sparse group kernel does
+// per row, on its own for the tests and the benchmarks.
+__global__ void __launch_bounds__(kHllBlock) pgx_sel_dir_find(const unsigned long long* __restrict__ keys, int64_t n,
+                                                              const SelSparseKey K, uint32_t* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kHllBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t h = K.W == 1 ? pgx_find<1>(K.keys, K.state, K.cap, {keys[i]}, K.cap)
+                             : pgx_find<2>(K.keys, K.state, K.cap, {keys[2 * i], keys[2 * i + 1]}, K.cap);
+  if (h < 0) atomicAdd(K.miss, 1ull);
+  out[i] = h < 0 ? kHllNoSlot : K.index[h];
+}
+
 }  // namespace pgx
+
+// keys: n keys of W words in device memory, distinct; check: the caller's host copy of them.  Of the table, tkey (cap x
+// W words) and, when W == 2, tstate (cap words) are cleared here, on the stream, before the build; tidx (cap words) is
+// not: only the entries of slots that hold a key are written, and only those are ever read.  Refused without launching
+// anything: a null pointer, a negative count or one over kSelMaxSparseGroups, a W other than 1 or 2, a capacity that
+// is not a power of two, is below the count or is above 2^20 (eight times the largest count: nothing needs more), and
+// a one-word key of ~0 (the empty slot).
+extern "C" hipError_t pgx_launch_sel_dir_build(const unsigned long long* keys, const unsigned long long* check,
+                                               int64_t n, int W, unsigned long long* tkey, unsigned int* tstate,
+                                               uint32_t* tidx, uint64_t cap, hipStream_t stream) {
+  if (!keys || !check || !tkey || !tidx || n < 0 || n > pgx::kSelMaxSparseGroups || (W != 1 && W != 2) ||
+      (W == 2 && !tstate) || cap == 0 || (cap & (cap - 1)) != 0 || cap < static_cast<uint64_t>(n) ||
+      cap > (1ull << 20))
+    return hipErrorInvalidValue;
+  if (W == 1)
+    for (int64_t i = 0; i < n; ++i)
+      if (check[i] == ~0ull) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(tkey, 0xFF, cap * static_cast<uint64_t>(W) * 8, stream);
+  if (e == hipSuccess && W == 2) e = hipMemsetAsync(tstate, 0, cap * 4, stream);
+  if (e != hipSuccess || n == 0) return e;
+  const int64_t blocks = (n + pgx::kHllBlock - 1) / pgx::kHllBlock;
+  hipLaunchKernelGGL(pgx::pgx_sel_dir_build, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kHllBlock), 0, stream, keys,
+                     n, W, tkey, tstate, tidx, cap);
+  return hipGetLastError();
+}
+
+// out: n u32 (device).  key: the caller's host struct, checked as the sparse group launchers check it.
+extern "C" hipError_t pgx_launch_sel_dir_find(const unsigned long long* keys, int64_t n, const pgx::SelSparseKey* key,
+                                              uint32_t* out, hipStream_t stream) {
+  if (!keys || !out || n < 0 || n > (1ll << 24) || !pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const int64_t blocks = (n + pgx::kHllBlock - 1) / pgx::kHllBlock;
+  hipLaunchKernelGGL(pgx::pgx_sel_dir_find, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kHllBlock), 0, stream, keys,
+                     n, *key, out);
+  return hipGetLastError();
+}
 
 static bool hll_item_ok(const pgx::HllItem& h) { return pgx::sel_item_ok(h, 0) && h.codes; }
 
@@ -252,9 +344,22 @@ extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items,
                                                  int wgs_per_item, hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_hll_offer_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_hll_offer_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::HllGroupItem& g) { return hll_item_ok(g.h) && pgx::sel_gcols_host_ok(g.g, ngcols); },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+// The sparse form: every item's `h.out` is a table of key->groups x 256 u32 registers, zeroed by the caller; key: the
+// caller's host struct (its directory built by pgx_launch_sel_dir_build on the same stream).
+extern "C" hipError_t pgx_launch_hll_offer_group_sparse(const pgx::HllGroupItem* items,
+                                                        const pgx::HllGroupItem* check, int nitems,
+                                                        const pgx::SelSparseKey* key, int wgs_per_item,
+                                                        hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_hll_offer_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::HllGroupItem& g) { return hll_item_ok(g.h) && pgx::sel_gcols_host_ok(g.g, ngcols); }, *key);
 }
 
 // out: ngroups x 256 bytes (as ngroups x 64 dwords); group i's registers are those of table slot slot[i].
@@ -285,9 +390,23 @@ extern "C" hipError_t pgx_launch_hll_offer_mv_group(const pgx::HllMvGroupItem* i
                                                     hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_hll_offer_mv_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_hll_offer_mv_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::HllMvGroupItem& m) {
         return hll_item_ok(m.g.h) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
       },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+extern "C" hipError_t pgx_launch_hll_offer_mv_group_sparse(const pgx::HllMvGroupItem* items,
+                                                           const pgx::HllMvGroupItem* check, int nitems,
+                                                           const pgx::SelSparseKey* key, int wgs_per_item,
+                                                           hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_hll_offer_mv_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::HllMvGroupItem& m) {
+        return hll_item_ok(m.g.h) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
+      },
+      *key);
 }

@@ -41,7 +41,56 @@ __device__ __forceinline__ uint32_t sel_row_slot(const HllGCol* gc, const HllGro
   return s;
 }
 
-__device__ __forceinline__ bool sel_gcols_ok(const HllGCol* gc, const HllGroupKey& K) {
+// The same through the directory of a sparse run: the row's global ids packed into the directory's key and looked up
+// over the whole table.  The group's index, or kHllNoSlot for a key the directory does not hold (an id that does not
+// fit its field, a remap of -1 among them, is in no key); every such row is counted in *K.miss.
+__device__ __forceinline__ uint32_t sel_row_slot_sparse(const HllGCol* gc, const SelSparseKey& K, int32_t row) {
+  u64 k0 = 0ull, k1 = 0ull;
+  uint32_t bad = 0u;
+  for (int g = 0; g < K.ngcols; ++g) {
+    const uint32_t id = pgx_fwd_value(gc[g].fwd, row, gc[g].bits);
+    const uint32_t gid = gc[g].remap ? static_cast<uint32_t>(gc[g].remap[id]) : id;  // a negative id: >= 2^31
+    const uint32_t sh = K.shift[g];
+    bad |= static_cast<uint32_t>(static_cast<u64>(gid) >> K.bits[g]);  // (bits <= 31: a card is an int32)
+    const u64 lo = static_cast<u64>(gid) << sh;
+    const u64 hi = sh > 32u ? static_cast<u64>(gid) >> (64u - sh) : 0ull;  // the part past bit 64 (0 unless it straddles)
+    const u64 w1 = 0ull - static_cast<u64>(K.word[g]);                     // all ones: the field starts in word 1
+    k0 |= lo & ~w1;
+    k1 |= (lo & w1) | (hi & ~w1);
+  }
+  i64 h = -1;
+  if (bad == 0u)
+    h = K.W == 1 ? pgx_find<1>(K.keys, K.state, K.cap, {k0}, K.cap) : pgx_find<2>(K.keys, K.state, K.cap, {k0, k1}, K.cap);
+  if (h < 0) {
+    atomicAdd(K.miss, 1ull);
+    return kHllNoSlot;
+  }
+  return K.index[h];
+}
+
+// rows of the key's tables: a slot at or past it is never written
+__device__ __forceinline__ uint32_t sel_key_rows(const HllGroupKey& K) { return static_cast<uint32_t>(K.slots); }
+__device__ __forceinline__ uint32_t sel_key_rows(const SelSparseKey& K) { return K.groups; }
+__device__ __forceinline__ uint32_t sel_row_slot(const HllGCol* gc, const SelSparseKey& K, int32_t row) {
+  return sel_row_slot_sparse(gc, K, row);
+}
+
+// s[j]: the slot of row J0 + j of the mask word that starts at doc d0, j < 16, through a sparse run's directory: the
+// selected rows' lookups one after the other; a row that is not selected is not looked up (it would count as a miss)
+// and gets kHllNoSlot.  (The dense keys' 16 independent id loads per group column stand in the kernels themselves,
+// under `if constexpr`: moved into a function of their own they compiled into other code (pgx_percentile_count_group
+// into 106 VGPRs instead of 120, four kernels with one more SGPR), and the dense instantiations are to stay,
+// instruction for instruction, what they were.)
+template <int J0>
+__device__ __forceinline__ void sel_word_slots(const HllGCol* gc, const SelSparseKey& K, uint32_t sel, int32_t d0,
+                                               uint32_t (&s)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    s[j] = ((sel >> (J0 + j)) & 1u) != 0u ? sel_row_slot_sparse(gc, K, d0 + J0 + j) : kHllNoSlot;
+}
+
+template <class Key>
+__device__ __forceinline__ bool sel_gcols_ok(const HllGCol* gc, const Key& K) {
   bool ok = true;
   for (int g = 0; g < K.ngcols; ++g) ok = ok && gc[g].bits >= 1 && gc[g].bits <= 32;
   return ok;
@@ -139,41 +188,49 @@ __device__ __forceinline__ void sel_mv_walk(const Item& A, int words, const int3
 // dense word in passes of independent loads over its 32 docs (all inside the group columns' padded indexes; a doc that
 // is not selected takes remap entry 0), and parked in LDS (slot_of: 32 * kHllBlock words): one column of 32 per thread,
 // which only that thread touches.
-template <class Item, class Batch>
-__device__ __forceinline__ void sel_mv_group_walk(const Item& A, const HllGCol* gc, const HllGroupKey& K,
+template <class Item, class Key, class Batch>
+__device__ __forceinline__ void sel_mv_group_walk(const Item& A, const HllGCol* gc, const Key& K,
                                                   const int32_t* __restrict__ start, int32_t total, uint32_t* slot_of,
                                                   Batch batch) {
   const int tid = static_cast<int>(threadIdx.x);
   uint32_t* const mine = slot_of + tid;  // doc j of the word: mine[j * kHllBlock]
   const int words = sel_gcols_ok(gc, K) ? sel_mv_words(A, start, total) : 0;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+  const uint32_t slots32 = sel_key_rows(K);  // <= kHllMaxGroupSlots, sparse: <= kSelMaxSparseGroups (launcher)
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kHllBlock;
   for (int64_t w = static_cast<int64_t>(blockIdx.x) * kHllBlock + tid; w < words; w += stride) {
     const uint32_t sel = sel_mask_word(A, w);
     if (sel == 0u) continue;
     const int32_t d0 = static_cast<int32_t>(w * 32);
-    const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
-    for (int g = 0; g < K.ngcols; ++g) {
-      const uint32_t* __restrict__ gf = gc[g].fwd;
-      const int32_t* __restrict__ rm = gc[g].remap;
-      const int gb = gc[g].bits;
-      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
-      if (dense) {
+    if constexpr (std::is_same<Key, HllGroupKey>::value) {
+      const bool dense = __builtin_popcount(sel) >= kHllDenseRows;
+      for (int g = 0; g < K.ngcols; ++g) {
+        const uint32_t* __restrict__ gf = gc[g].fwd;
+        const int32_t* __restrict__ rm = gc[g].remap;
+        const int gb = gc[g].bits;
+        const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+        if (dense) {
 #pragma unroll 8
-        for (int j = 0; j < 32; ++j) {
-          const uint32_t on = 0u - ((sel >> j) & 1u);
-          const uint32_t id = pgx_fwd_value2(gf, d0 + j, gb) & on;
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+          for (int j = 0; j < 32; ++j) {
+            const uint32_t on = 0u - ((sel >> j) & 1u);
+            const uint32_t id = pgx_fwd_value2(gf, d0 + j, gb) & on;
+            const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;  // a negative id: >= 2^31
+            mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+          }
+        } else {
+          for (uint32_t m = sel; m;) {
+            const int j = __builtin_ctz(m);
+            m &= m - 1u;
+            const uint32_t id = pgx_fwd_value(gf, d0 + j, gb);
+            const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
+            mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
+          }
         }
-      } else {
-        for (uint32_t m = sel; m;) {
-          const int j = __builtin_ctz(m);
-          m &= m - 1u;
-          const uint32_t id = pgx_fwd_value(gf, d0 + j, gb);
-          const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
-          mine[j * kHllBlock] = hll_mv_fold(g == 0 ? 0u : mine[j * kHllBlock], gid, mul);
-        }
+      }
+    } else {  // a sparse run: one directory lookup per selected doc
+      for (uint32_t m = sel; m;) {
+        const int j = __builtin_ctz(m);
+        m &= m - 1u;
+        mine[j * kHllBlock] = sel_row_slot_sparse(gc, K, d0 + j);
       }
     }
     for (uint32_t m = sel; m;) {
@@ -195,6 +252,19 @@ inline bool sel_key_ok(int ngcols, const uint64_t* gmul, int64_t slots) {
   if (!gmul || ngcols < 1 || ngcols > kMaxGroupCols || slots < 1 || slots > kHllMaxGroupSlots) return false;
   for (int g = 0; g < ngcols; ++g)
     if (gmul[g] < 1 || gmul[g] > static_cast<uint64_t>(slots)) return false;  // a mixed-radix layout
+  return true;
+}
+// the sparse forms' key, a host struct: the directory is there and sized, every field lies inside the key's W words
+inline bool sel_sparse_key_ok(const SelSparseKey* K) {
+  if (!K || !K->keys || !K->index || !K->miss || (K->W != 1 && K->W != 2) || (K->W == 2 && !K->state)) return false;
+  if (K->groups < 1u || K->groups > static_cast<uint32_t>(kSelMaxSparseGroups)) return false;
+  if (K->cap == 0 || (K->cap & (K->cap - 1)) != 0 || K->cap < K->groups) return false;
+  if (K->ngcols < 1 || K->ngcols > kMaxGroupCols) return false;
+  for (int g = 0; g < K->ngcols; ++g) {
+    const int first = 64 * K->word[g] + K->shift[g];
+    if (K->bits[g] < 1 || K->bits[g] > 32 || K->shift[g] > 63 || K->word[g] > 1 || first + K->bits[g] > 64 * K->W)
+      return false;
+  }
   return true;
 }
 inline bool sel_gcols_host_ok(const HllGCol* gc, int ngcols) {

@@ -175,6 +175,36 @@ extern "C" hipError_t pgx_launch_percentile_emit(const uint64_t* table, int32_t 
                                                  const int64_t* off, int64_t nrows, int64_t slots, int32_t* ids,
                                                  uint64_t* counts, int64_t capacity, int wgs_per_row, int wgs,
                                                  hipStream_t stream);
+// the sparse forms (PGX_X_SPARSE_GROUP_SETS): tables of one row per group of the result, slots through a directory
+extern "C" hipError_t pgx_launch_sel_dir_build(const unsigned long long* keys, const unsigned long long* check,
+                                               int64_t n, int W, unsigned long long* tkey, unsigned int* tstate,
+                                               uint32_t* tidx, uint64_t cap, hipStream_t stream);
+extern "C" hipError_t pgx_launch_sel_dir_find(const unsigned long long* keys, int64_t n, const pgx::SelSparseKey* key,
+                                              uint32_t* out, hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer_group_sparse(const pgx::HllGroupItem* items,
+                                                        const pgx::HllGroupItem* check, int nitems,
+                                                        const pgx::SelSparseKey* key, int wgs_per_item,
+                                                        hipStream_t stream);
+extern "C" hipError_t pgx_launch_hll_offer_mv_group_sparse(const pgx::HllMvGroupItem* items,
+                                                           const pgx::HllMvGroupItem* check, int nitems,
+                                                           const pgx::SelSparseKey* key, int wgs_per_item,
+                                                           hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark_group_sparse(const pgx::DistinctGroupItem* items,
+                                                            const pgx::DistinctGroupItem* check, int nitems,
+                                                            const pgx::SelSparseKey* key, int wgs_per_item,
+                                                            hipStream_t stream);
+extern "C" hipError_t pgx_launch_distinct_mark_mv_group_sparse(const pgx::DistinctMvGroupItem* items,
+                                                               const pgx::DistinctMvGroupItem* check, int nitems,
+                                                               const pgx::SelSparseKey* key, int wgs_per_item,
+                                                               hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count_group_sparse(const pgx::PercentileGroupItem* items,
+                                                               const pgx::PercentileGroupItem* check, int nitems,
+                                                               const pgx::SelSparseKey* key, int wgs_per_item,
+                                                               hipStream_t stream);
+extern "C" hipError_t pgx_launch_percentile_count_mv_group_sparse(const pgx::PercentileMvGroupItem* items,
+                                                                  const pgx::PercentileMvGroupItem* check,
+                                                                  int nitems, const pgx::SelSparseKey* key,
+                                                                  int wgs_per_item, hipStream_t stream);
 struct pgx_ctx;
 extern "C" void ctx_unref(pgx_ctx* ctx);
 
@@ -1215,7 +1245,8 @@ struct SelScan {
   const ExecPlan* P = nullptr;
   pgx_segment* const* segs = nullptr;
   int n = 0, ng = 0;
-  uint64_t slots = 1;
+  uint64_t slots = 1;    // rows of every table: the key space's slots; a sparse run: the result's groups
+  const pgx::SelSparseKey* sparse = nullptr;  // a sparse run's key and directory (the group launches take it)
   int wgs = 1;           // workgroups per item
   bool scanned = false;  // false: every segment empty, nothing is launched and the outputs stay zero
   hipStream_t st = nullptr;
@@ -1266,16 +1297,17 @@ struct SelItems {
     mdev = put(ctx, st, mv, gmv, mv_what);
   }
 
-  // One launch over the single-value items, one over the multi-value ones: of the plain or of the group kernel.
-  template <class L, class GL>
+  // One launch over the single-value items, one over the multi-value ones: of the plain or of the group kernel (a
+  // sparse run: of the group kernel's sparse form, timed as sname).
+  template <class L, class GL, class SL>
   void launch_sv(const SelScan& S, const char* name, L plain, const char* what, const char* gname, GL group,
-                 const char* gwhat) const {
-    run(S, sdev, sv, gsv, name, plain, what, gname, group, gwhat);
+                 const char* gwhat, const char* sname, SL sparse) const {
+    run(S, sdev, sv, gsv, name, plain, what, gname, group, gwhat, sname, sparse);
   }
-  template <class L, class GL>
+  template <class L, class GL, class SL>
   void launch_mv(const SelScan& S, const char* name, L plain, const char* what, const char* gname, GL group,
-                 const char* gwhat) const {
-    run(S, mdev, mv, gmv, name, plain, what, gname, group, gwhat);
+                 const char* gwhat, const char* sname, SL sparse) const {
+    run(S, mdev, mv, gmv, name, plain, what, gname, group, gwhat, sname, sparse);
   }
 
  private:
@@ -1287,12 +1319,15 @@ struct SelItems {
     if (bytes) hip_check(hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, st), what);
     return d;
   }
-  template <class A, class B, class L, class GL>
+  template <class A, class B, class L, class GL, class SL>
   static void run(const SelScan& S, const DevBuf& dev, const std::vector<A>& a, const std::vector<B>& b,
-                  const char* name, L plain, const char* what, const char* gname, GL group, const char* gwhat) {
+                  const char* name, L plain, const char* what, const char* gname, GL group, const char* gwhat,
+                  const char* sname, SL sparse) {
     if (!S.scanned) return;
     if (!a.empty()) PGX_LAUNCH(S.st, name, plain(dev.as<A>(), a.data(), int(a.size()), S.wgs, S.st), what);
-    if (!b.empty())
+    if (!b.empty() && S.sparse)
+      PGX_LAUNCH(S.st, sname, sparse(dev.as<B>(), b.data(), int(b.size()), S.sparse, S.wgs, S.st), gwhat);
+    else if (!b.empty())
       PGX_LAUNCH(S.st, gname,
                  group(dev.as<B>(), b.data(), int(b.size()), S.ng, S.P->kq.gmul, int64_t(S.slots), S.wgs, S.st), gwhat);
   }
@@ -1300,6 +1335,27 @@ struct SelItems {
 using HllItems = SelItems<pgx::HllItem, pgx::HllGroupItem, pgx::HllMvItem, pgx::HllMvGroupItem>;
 using DistinctItems =
     SelItems<pgx::DistinctItem, pgx::DistinctGroupItem, pgx::DistinctMvItem, pgx::DistinctMvGroupItem>;
+
+// The result kernels' launchers (pgx_hll_narrow, pgx_distinct_count / _emit, pgx_percentile_sizes / _emit) take up to
+// kHllMaxGroupSlots rows of a table of up to as many slots.  A sparse run's tables hold one row per group in the
+// result's order (row i is group i) and may hold more: they go in stretches of that many groups, each a table of its
+// own whose rows are 0, 1, ...: f(first group, groups, slots of the stretch's table).
+template <class F>
+void sel_result_stretches(size_t groups, uint64_t slots, F f) {
+  if (slots <= uint64_t(pgx::kHllMaxGroupSlots)) {
+    f(size_t(0), groups, slots);
+    return;
+  }
+  for (size_t c0 = 0; c0 < groups; c0 += size_t(pgx::kHllMaxGroupSlots)) {
+    const size_t cn = std::min(groups - c0, size_t(pgx::kHllMaxGroupSlots));
+    f(c0, cn, uint64_t(cn));
+  }
+}
+inline void sel_result_rows_ok(const std::vector<int64_t>& rows, uint64_t slots) {
+  if (slots <= uint64_t(pgx::kHllMaxGroupSlots)) return;
+  for (size_t i = 0; i < rows.size(); ++i)
+    if (rows[i] != int64_t(i)) fail(PGX_ERR_INTERNAL, "a table of over PGX_HLL_MAX_GROUP_SLOTS rows, not in the result's order");
+}
 
 // ---- pgx_distinct.cpp: DISTINCTCOUNT / DISTINCTCOUNTMV inside run_hll ----------------------------------------------
 // One presence bitmap per (column, distinct dictionary): slots rows of `words` u32.  Segments whose dictionaries are

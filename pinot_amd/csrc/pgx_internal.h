@@ -252,6 +252,29 @@ struct HllGroupKey {           // passed by value: slot = sum over the group col
   int32_t ngcols;
   int32_t pad;
 };
+// The sparse counterpart (PGX_X_SPARSE_GROUP_SETS): the tables hold one row per group of the result, and a row's group
+// is looked up in a directory -- an open-addressing table (pgx_insert / pgx_find, pgx_device.h) from the row's packed
+// key to the group's index, built by pgx_sel_dir_build from the result's keys.  The key is the directory's own: field g
+// is group column g's global id in bits[g] = ceil(log2(global cardinality)) bits (at least 1), the fields packed one
+// after the other from bit 0 of a 128-bit word (field g starts at bit 64 * word[g] + shift[g]; one that straddles bit
+// 64 continues in word 1).  W: key words per table slot, 1 (keys of up to 64 bits, none of them ~0: that is the empty
+// slot) or 2.
+constexpr int kSelMaxSparseGroups = 131072;  // pgx.h PGX_SET_MAX_SPARSE_GROUPS; every index is below kHllNoSlot
+struct SelSparseKey {          // passed by value
+  const unsigned long long* keys;   // cap x W words
+  const unsigned int* state;        // cap (W == 2; not read when W == 1)
+  const uint32_t* index;            // cap: the group of the key in that slot
+  unsigned long long* miss;         // rows whose key the directory does not hold
+  uint64_t cap;                     // a power of two, >= groups
+  uint8_t shift[kMaxGroupCols];
+  uint8_t word[kMaxGroupCols];
+  uint8_t bits[kMaxGroupCols];
+  uint32_t groups;                  // 1 .. kSelMaxSparseGroups
+  int32_t W;
+  int32_t ngcols;
+  int32_t pad;
+};
+static_assert(sizeof(SelSparseKey) == 40 + 3 * kMaxGroupCols + 16, "tests/sel_dir_ref.py mirrors this");
 
 // DISTINCTCOUNT / DISTINCTCOUNTMV (pgx_distinct.hip; DistinctCountAggregationFunction): one item per (segment,
 // function), laid out like the HLL items.  The state is one presence bit per dictId, (card + 31) / 32 u32 words per

@@ -55,10 +55,12 @@ void percentile_count(pgx_ctx* ctx, const SelScan& S, PercentileRun& Q) {
     }
   Q.items.upload(ctx, S.st, "PERCENTILE items H2D", "PERCENTILEMV items H2D");
   Q.items.launch_sv(S, "pgx_percentile_count", pgx_launch_percentile_count, "PERCENTILE counts",
-                    "pgx_percentile_count_group", pgx_launch_percentile_count_group, "PERCENTILE group counts");
+                    "pgx_percentile_count_group", pgx_launch_percentile_count_group, "PERCENTILE group counts",
+                    "pgx_percentile_count_group_sparse", pgx_launch_percentile_count_group_sparse);
   Q.items.launch_mv(S, "pgx_percentile_count_mv", pgx_launch_percentile_count_mv, "PERCENTILEMV counts",
                     "pgx_percentile_count_mv_group", pgx_launch_percentile_count_mv_group,
-                    "PERCENTILEMV group counts");
+                    "PERCENTILEMV group counts", "pgx_percentile_count_mv_group_sparse",
+                    pgx_launch_percentile_count_mv_group_sparse);
 }
 
 // the double the reference's Dictionary.getDoubleValue gives for dictId i
@@ -76,6 +78,7 @@ void percentile_collect(pgx_ctx* ctx, PercentileRun& Q, const std::vector<int64_
   R->pct_values.assign(nq, {});
   R->pct_counts.assign(nq, {});
   if (nq == 0 || groups == 0) return;
+  sel_result_rows_ok(rows, slots);
   const int budget = 8 * std::max(1, ctx->num_cus);
   const int wgs = int(std::min<size_t>(groups, size_t(budget)));
   DevBuf rdev(ctx, groups * 8);
@@ -96,10 +99,13 @@ void percentile_collect(pgx_ctx* ctx, PercentileRun& Q, const std::vector<int64_
       p.sizes.assign(groups, 0);
       if (t.col->card >= 1) {
         p.sdev = DevBuf(ctx, groups * 4);
-        PGX_LAUNCH(st, "pgx_percentile_sizes",
-                   pgx_launch_percentile_sizes(t.table.as<uint64_t>(), t.col->card, rdev.as<int64_t>(),
-                                               int64_t(groups), int64_t(slots), p.sdev.as<uint32_t>(), wgs, st),
-                   "PERCENTILE sizes");
+        sel_result_stretches(groups, slots, [&](size_t c0, size_t cn, uint64_t cs) {
+          PGX_LAUNCH(st, "pgx_percentile_sizes",
+                     pgx_launch_percentile_sizes(t.table.as<uint64_t>() + c0 * size_t(t.col->card), t.col->card,
+                                                 rdev.as<int64_t>(), int64_t(cn), int64_t(cs),
+                                                 p.sdev.as<uint32_t>() + c0, wgs, st),
+                     "PERCENTILE sizes");
+        });
         hip_check(hipMemcpyAsync(p.sizes.data(), p.sdev.p, groups * 4, hipMemcpyDeviceToHost, st),
                   "PERCENTILE sizes D2H");
       }
@@ -122,11 +128,13 @@ void percentile_collect(pgx_ctx* ctx, PercentileRun& Q, const std::vector<int64_
       p.counts.assign(size_t(total), 0);
       hip_check(hipMemcpyAsync(p.odev.p, p.off.data(), groups * 8, hipMemcpyHostToDevice, st),
                 "PERCENTILE offsets H2D");
-      PGX_LAUNCH(st, "pgx_percentile_emit",
-                 pgx_launch_percentile_emit(p.t->table.as<uint64_t>(), p.t->col->card, rdev.as<int64_t>(),
-                                            p.odev.as<int64_t>(), int64_t(groups), int64_t(slots),
-                                            p.idev.as<int32_t>(), p.cdev.as<uint64_t>(), total, per_row, wgs, st),
-                 "PERCENTILE pairs");
+      sel_result_stretches(groups, slots, [&](size_t c0, size_t cn, uint64_t cs) {
+        PGX_LAUNCH(st, "pgx_percentile_emit",
+                   pgx_launch_percentile_emit(p.t->table.as<uint64_t>() + c0 * size_t(card), p.t->col->card,
+                                              rdev.as<int64_t>(), p.odev.as<int64_t>() + c0, int64_t(cn), int64_t(cs),
+                                              p.idev.as<int32_t>(), p.cdev.as<uint64_t>(), total, per_row, wgs, st),
+                   "PERCENTILE pairs");
+      });
       hip_check(hipMemcpyAsync(p.ids.data(), p.idev.p, size_t(total) * 4, hipMemcpyDeviceToHost, st),
                 "PERCENTILE dictIds D2H");
       hip_check(hipMemcpyAsync(p.counts.data(), p.cdev.p, size_t(total) * 8, hipMemcpyDeviceToHost, st),

@@ -97,24 +97,28 @@ __global__ void __launch_bounds__(kHllBlock) pgx_percentile_count(const Percenti
 // Rows J0 .. J0 + 15 of a mask word whose dictIds are decoded (v): slots, then the adds.  Half a word at a time, as in
 // pgx_distinct_mark_group: 16 loads in flight per lane and pass.  The word's rows all lie inside the group columns'
 // padded indexes, so the id loads are unconditional; a row that counts nothing takes remap entry 0.
-template <int J0, class C>
-__device__ __forceinline__ void pct_group_rows(C* ctr, const PercentileGroupItem& G, const HllGroupKey& K,
-                                               uint32_t sel, int32_t d0, const uint32_t (&v)[32]) {
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);  // <= kHllMaxGroupSlots (launcher)
+template <int J0, class C, class Key>
+__device__ __forceinline__ void pct_group_rows(C* ctr, const PercentileGroupItem& G, const Key& K, uint32_t sel,
+                                               int32_t d0, const uint32_t (&v)[32]) {
+  const uint32_t slots32 = sel_key_rows(K);  // <= kHllMaxGroupSlots, sparse: <= kSelMaxSparseGroups (launcher)
   const uint32_t card = static_cast<uint32_t>(G.d.card);
   uint32_t s[16];
-  for (int g = 0; g < K.ngcols; ++g) {
-    const uint32_t* __restrict__ gf = G.g[g].fwd;
-    const int32_t* __restrict__ rm = G.g[g].remap;
-    const int gb = G.g[g].bits;
-    const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
+  if constexpr (std::is_same<Key, HllGroupKey>::value) {
+    for (int g = 0; g < K.ngcols; ++g) {
+      const uint32_t* __restrict__ gf = G.g[g].fwd;
+      const int32_t* __restrict__ rm = G.g[g].remap;
+      const int gb = G.g[g].bits;
+      const uint32_t mul = static_cast<uint32_t>(K.gmul[g]);  // 1..slots (launcher)
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t on = 0u - ((sel >> (J0 + j)) & 1u);
-      const uint32_t id = pgx_fwd_value2(gf, d0 + J0 + j, gb) & on;
-      const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
-      s[j] = hll_mv_fold(g == 0 ? 0u : s[j], gid, mul);
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t on = 0u - ((sel >> (J0 + j)) & 1u);
+        const uint32_t id = pgx_fwd_value2(gf, d0 + J0 + j, gb) & on;
+        const uint32_t gid = rm ? static_cast<uint32_t>(rm[id]) : id;
+        s[j] = hll_mv_fold(g == 0 ? 0u : s[j], gid, mul);
+      }
     }
+  } else {
+    sel_word_slots<J0>(G.g, K, sel, d0, s);
   }
 #pragma unroll
   for (int j = 0; j < 16; ++j)
@@ -122,10 +126,10 @@ __device__ __forceinline__ void pct_group_rows(C* ctr, const PercentileGroupItem
       pct_add(ctr, static_cast<size_t>(s[j]) * card + v[J0 + j]);
 }
 
-template <class C>
-__device__ __forceinline__ void pct_group_scan(C* ctr, const PercentileGroupItem& G, const HllGroupKey& K, int words) {
+template <class C, class Key>
+__device__ __forceinline__ void pct_group_scan(C* ctr, const PercentileGroupItem& G, const Key& K, int words) {
   const PercentileItem& A = G.d;
-  const uint32_t slots32 = static_cast<uint32_t>(K.slots);
+  const uint32_t slots32 = sel_key_rows(K);
   const uint32_t card = static_cast<uint32_t>(A.card);
   sel_walk(
       A, words,
@@ -142,14 +146,19 @@ __device__ __forceinline__ void pct_group_scan(C* ctr, const PercentileGroupItem
       });
 }
 
-// counters of a group table when it is counted in LDS, else 0: slots <= 65536 and card < 2^31, so no overflow
-__device__ __forceinline__ uint32_t pct_lds_counters(const HllGroupKey& K, int32_t card) {
-  const uint64_t n = K.slots * static_cast<uint64_t>(card > 0 ? card : 0);
+// counters of a group table when it is counted in LDS, else 0: rows <= 131072 and card < 2^31, so no overflow
+__device__ __forceinline__ uint64_t pct_key_rows64(const HllGroupKey& K) { return K.slots; }
+__device__ __forceinline__ uint64_t pct_key_rows64(const SelSparseKey& K) { return K.groups; }
+template <class Key>
+__device__ __forceinline__ uint32_t pct_lds_counters(const Key& K, int32_t card) {
+  const uint64_t n = pct_key_rows64(K) * static_cast<uint64_t>(card > 0 ? card : 0);
   return n <= static_cast<uint64_t>(kPercentileLdsCounters) ? static_cast<uint32_t>(n) : 0u;
 }
 
+// Key: HllGroupKey or SelSparseKey (pgx_hll_offer_group); only the slot computation differs.
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_percentile_count_group(const PercentileGroupItem* __restrict__ items,
-                                                                        int nitems, const HllGroupKey K) {
+                                                                        int nitems, const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t lc[kPercentileLdsCounters];
@@ -210,8 +219,9 @@ __global__ void __launch_bounds__(kHllBlock) pgx_percentile_count_mv(const Perce
 }
 
 // The same into the slots' rows: every value of a doc into the row of the doc's slot (sel_mv_group_walk).
+template <class Key>
 __global__ void __launch_bounds__(kHllBlock) pgx_percentile_count_mv_group(
-    const PercentileMvGroupItem* __restrict__ items, int nitems, const HllGroupKey K) {
+    const PercentileMvGroupItem* __restrict__ items, int nitems, const Key K) {
   const int item = static_cast<int>(blockIdx.y);
   if (item >= nitems) return;
   __shared__ uint32_t slot_of[32 * kHllBlock];
@@ -325,9 +335,22 @@ extern "C" hipError_t pgx_launch_percentile_count_group(const pgx::PercentileGro
                                                         hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_percentile_count_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_percentile_count_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::PercentileGroupItem& g) { return pct_item_ok(g.d) && pgx::sel_gcols_host_ok(g.g, ngcols); },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+// The sparse forms: every item's `out` holds key->groups rows; key: the caller's host struct (pgx_hll.hip).
+extern "C" hipError_t pgx_launch_percentile_count_group_sparse(const pgx::PercentileGroupItem* items,
+                                                               const pgx::PercentileGroupItem* check, int nitems,
+                                                               const pgx::SelSparseKey* key, int wgs_per_item,
+                                                               hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_percentile_count_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::PercentileGroupItem& g) { return pct_item_ok(g.d) && pgx::sel_gcols_host_ok(g.g, ngcols); },
+      *key);
 }
 
 // The start arrays are device data, so the kernels clamp every value range to `total`.
@@ -345,11 +368,25 @@ extern "C" hipError_t pgx_launch_percentile_count_mv_group(const pgx::Percentile
                                                            int wgs_per_item, hipStream_t stream) {
   if (!pgx::sel_key_ok(ngcols, gmul, slots)) return hipErrorInvalidValue;
   return pgx::sel_launch(
-      pgx::pgx_percentile_count_mv_group, items, check, nitems, wgs_per_item, stream,
+      pgx::pgx_percentile_count_mv_group<pgx::HllGroupKey>, items, check, nitems, wgs_per_item, stream,
       [&](const pgx::PercentileMvGroupItem& m) {
         return pct_item_ok(m.g.d) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
       },
       pgx::sel_key(ngcols, gmul, slots));
+}
+
+extern "C" hipError_t pgx_launch_percentile_count_mv_group_sparse(const pgx::PercentileMvGroupItem* items,
+                                                                  const pgx::PercentileMvGroupItem* check,
+                                                                  int nitems, const pgx::SelSparseKey* key,
+                                                                  int wgs_per_item, hipStream_t stream) {
+  if (!pgx::sel_sparse_key_ok(key)) return hipErrorInvalidValue;
+  const int ngcols = key->ngcols;
+  return pgx::sel_launch(
+      pgx::pgx_percentile_count_mv_group<pgx::SelSparseKey>, items, check, nitems, wgs_per_item, stream,
+      [&](const pgx::PercentileMvGroupItem& m) {
+        return pct_item_ok(m.g.d) && pgx::sel_gcols_host_ok(m.g.g, ngcols) && pgx::sel_mv_ok(m.start, m.total);
+      },
+      *key);
 }
 
 // table: slots rows of card u64 counters; rows: nrows row indexes (int64, device); sizes: nrows u32 (device).

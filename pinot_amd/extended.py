@@ -183,6 +183,18 @@ def native_percentile(request: dict, segments) -> bool:
     return not _star_tree_request(request, segments)
 
 
+def sparse_sets_flag() -> int:
+    """The execution flag of a group-by base query that holds native functions (``native_hll``, ``native_distinct``,
+    ``native_percentile``): PGX_X_SPARSE_GROUP_SETS, with which the library also takes key spaces that are not dense or
+    have more than PGX_HLL_MAX_GROUP_SLOTS slots (tables of one row per group of the result).  What it still refuses
+    (PGX_ERR_UNSUPPORTED) runs as the next route of ``run``, down to the decomposition.  The flag is passed only with
+    PGX_SPARSE_SETS_NATIVE=1 (read here, at every request).  Without it, or with PGX_SPARSE_SETS_NATIVE=0, such key
+    spaces are refused at once and decomposed, as before the flag: the plan maker's route for them is pinned by
+    tests/test_gpu_percentile.py and tests/test_gpu_distinct.py (no native histogram or set is read for a refused
+    shape), so the sparse route through the plan maker is opt-in, as it is at the ABI."""
+    return N.PGX_X_SPARSE_GROUP_SETS if os.environ.get("PGX_SPARSE_SETS_NATIVE", "0") == "1" else 0
+
+
 def _is_hist_slot(s) -> bool:
     return isinstance(s, tuple) and s[0] == "hist"
 
@@ -279,7 +291,7 @@ def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -
     gb = request["group_by"]
     base, slot = _base_request(request, native)
     bq = E._Query(ctx, {"aggregations": base, "group_by": dict(gb), "filter": request.get("filter")})
-    r = bq.execute(segments)
+    r = bq.execute(segments, flags=sparse_sets_flag() if native else 0)
     try:
         bblk = E.decode_result(bq, r, segments, trim=combine)
     finally:
