@@ -42,7 +42,8 @@ extern "C" {
                               * pgx_result_select_* were added under 8: new entry points only, no existing struct or
                               * call changed; likewise PGX_DISTINCTCOUNTHLL[MV], pgx_result_hll and pgx_hll_codes, and
                               * PGX_DISTINCTCOUNT[MV], pgx_result_distinct[_counts] and pgx_java_hash_codes, and
-                              * PGX_PERCENTILE[MV], pgx_result_percentile[_counts] and pgx_histogram_percentile */
+                              * PGX_PERCENTILE[MV], pgx_result_percentile[_counts] and pgx_histogram_percentile, and
+                              * PGX_FASTHLL and pgx_fasthll_registers */
 
 typedef enum {
   PGX_OK = 0,
@@ -68,12 +69,14 @@ typedef enum { PGX_INT = 0, PGX_LONG = 1, PGX_FLOAT = 2, PGX_DOUBLE = 3, PGX_STR
  * PGX_PERCENTILE (PercentileAggregationFunction.java) and PGX_PERCENTILEMV (PercentileMVAggregationFunction.java): the
  * intermediate is the multiset of the selected values, held as (value, count) pairs and read with
  * pgx_result_percentile_counts and pgx_result_percentile (below, "PERCENTILE").  The multi-value form has the lower
- * code on purpose: code 14 on a single-value column is refused at compile time. */
+ * code on purpose: code 14 on a single-value column is refused at compile time.
+ * PGX_FASTHLL (FastHllAggregationFunction.java): a single-value STRING column of serialized HyperLogLogs; the
+ * intermediate is the 256 registers of their union, read with pgx_result_hll (below, "FASTHLL"). */
 typedef enum { PGX_COUNT = 0, PGX_SUM = 1, PGX_MIN = 2, PGX_MAX = 3, PGX_AVG = 4,
                PGX_COUNTMV = 5, PGX_SUMMV = 6, PGX_MINMV = 7, PGX_MAXMV = 8, PGX_AVGMV = 9,
                PGX_DISTINCTCOUNTHLL = 10, PGX_DISTINCTCOUNTHLLMV = 11,
                PGX_DISTINCTCOUNT = 12, PGX_DISTINCTCOUNTMV = 13,
-               PGX_PERCENTILEMV = 14, PGX_PERCENTILE = 15 } pgx_agg_fn;
+               PGX_PERCENTILEMV = 14, PGX_PERCENTILE = 15, PGX_FASTHLL = 16 } pgx_agg_fn;
 
 /* Predicate kinds (common/Predicate.java Type); they select the physical filter operator exactly as
  * plan/FilterPlanNode.java:118-132 does and drive the numEntriesScannedInFilter statistic. */
@@ -392,7 +395,7 @@ pgx_status pgx_result_gather(const pgx_result* r, const int64_t* group_index, in
  * groups in the order of pgx_result_group_keys / _values; an aggregation-only result has exactly one group
  * (first_group 0, num_groups 1).  The registers are those of stream-lib's HyperLogLog(log2m = 8) after
  * offer((int) hashCode(value)) of every selected doc's value: exact, whatever the order.  PGX_ERR_INVALID_ARG: agg_index
- * is not a PGX_DISTINCTCOUNTHLL[MV] function, or the range lies outside the result.
+ * is not a PGX_DISTINCTCOUNTHLL[MV] or PGX_FASTHLL function, or the range lies outside the result.
  * PGX_DISTINCTCOUNTHLLMV offers every value of every selected doc of a multi-value column (one slot per doc under
  * GROUP BY: the doc's single-value group columns).  Same registers, same accessor, same statistics: its column counts
  * once among the projected ones (docs x columns, not docs x values).  It mixes with PGX_DISTINCTCOUNTHLL and the
@@ -504,6 +507,35 @@ pgx_status pgx_result_percentile(const pgx_result* r, int32_t agg_index, int64_t
  * 32 bits: counts may sum past 2^31. */
 pgx_status pgx_histogram_percentile(const double* values, const int64_t* counts, int64_t n, int32_t percentile,
                                     double* out);
+
+/* ---- FASTHLL ------------------------------------------------------------------------------------
+ * PGX_FASTHLL takes a single-value STRING column whose values are HyperLogLogs of log2m 8 as
+ * startree/hll/HllUtil.java convertHllToString writes them: 180 chars, char = byte + 129 over HyperLogLog.getBytes().
+ * The intermediate is the register-wise maximum over the selected docs' estimators (FastHllAggregationFunction.java:
+ * addAll into a fresh HyperLogLog(8)), read with pgx_result_hll as a PGX_DISTINCTCOUNTHLL function's; every other
+ * accessor treats the index as an HLL index.  The maximum is idempotent, so the registers are a function of the set of
+ * dictIds selected: the query marks DISTINCTCOUNT's presence bitmaps (a set of their own, counted on their own
+ * against PGX_DISTINCT_MAX_TABLE_BYTES) and folds the set bits' rows of a per-dictionary register image -- 256 bytes
+ * per dictId in device memory, built on the first query over the dictionary -- into the result's groups on the device;
+ * segments with different dictionaries fold into the same registers.  The function mixes with the standard
+ * single-value functions and with codes 10-15 in any order and runs in the same scan; two of them over one column share
+ * their state; statistics are those of the HLL forms.
+ * pgx_query_compile returns PGX_ERR_UNSUPPORTED when every staged segment of the context that holds the column holds
+ * it multi-value or not as STRING; a column no staged segment has compiles, and the execution checks its own segments.
+ * PGX_ERR_UNSUPPORTED (the caller falls back): every limit of the HLL forms above, PGX_X_SPARSE_GROUP_SETS lifting the
+ * same one (the sparse route counts FASTHLL's u32 registers against PGX_HLL_MAX_TABLE_BYTES too); a multi-value or
+ * non-STRING column; a dictionary value that is not such an estimator (the reference throws there); register images
+ * of the query's distinct dictionaries of more than PGX_FASTHLL_MAX_IMAGE_BYTES in all, refused before anything is
+ * allocated or launched. */
+#define PGX_FASTHLL_MAX_IMAGE_BYTES (256u << 20)
+/* Host only, no device needed: registers[i * 256 + j] = register j of value i, the rows of the register image.
+ * values_utf8: the values' UTF-8 bytes back to back with n + 1 ascending offsets.  Per value: byte = (byte)(UTF-16 code
+ * unit - 129) (HllUtil.convertStringToHll), then HyperLogLog.Builder.build: big-endian log2m and byte count, then 43
+ * big-endian words of six 5-bit registers (register i: word i / 6, shift 5 * (i % 6)).  A value that is not a 180-byte
+ * estimator of log2m 8 (wrong length, log2m or byte count) returns PGX_ERR_UNSUPPORTED with its index in *bad_index
+ * (may be NULL; -1 when no value is bad); rows before it are written. */
+pgx_status pgx_fasthll_registers(const void* values_utf8, const int32_t* string_offsets, int64_t n, uint8_t* registers,
+                                 int64_t* bad_index);
 
 /* Dense-table layout for PGX_X_KEEP_DENSE_ON_DEVICE (multi-GPU RCCL merge):
  * slots = product of group cardinalities; buffer = (1 + num_aggs) planes of slots x 8 bytes.

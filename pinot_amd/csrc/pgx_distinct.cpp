@@ -39,11 +39,11 @@ void distinct_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots
       D.map_of[k][size_t(s)] = int(b);
     }
   if (bytes > uint64_t(PGX_DISTINCT_MAX_TABLE_BYTES))
-    fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNT: presence bitmaps over PGX_DISTINCT_MAX_TABLE_BYTES");
+    fail(PGX_ERR_UNSUPPORTED, std::string(D.fn) + ": presence bitmaps over PGX_DISTINCT_MAX_TABLE_BYTES");
   for (auto& maps : D.maps)
     for (auto& m : maps) {
       m.table = DevBuf(ctx, size_t(slots) * m.words * 4);
-      m.hash = distinct_hash_table(ctx, *m.col);
+      if (D.hashes) m.hash = distinct_hash_table(ctx, *m.col);
     }
 }
 
@@ -58,7 +58,7 @@ void distinct_mark(pgx_ctx* ctx, const SelScan& S, DistinctRun& D) {
       pgx::DistinctItem d{};
       d.out = D.maps[k][size_t(D.map_of[k][size_t(s)])].table.as<uint32_t>();
       d.card = col.card;
-      D.items.add(S, s, col, D.mv[k], "DISTINCTCOUNT", d);
+      D.items.add(S, s, col, D.mv[k], D.fn, d);
     }
   D.items.upload(ctx, S.st, "DISTINCTCOUNT items H2D", "DISTINCTCOUNTMV items H2D");
   D.items.launch_sv(S, "pgx_distinct_mark", pgx_launch_distinct_mark, "DISTINCTCOUNT marks",

@@ -1,6 +1,7 @@
 // libpgx: the boxed Java values' hashCode() in Java int arithmetic, and the union of hash-code lists.  Host only and
 // free of device code: pgx_hll.cpp (the HLL code tables, pgx_hll_codes, the DISTINCTCOUNT hash tables,
-// pgx_java_hash_codes), pgx_distinct.cpp (the per-group union) and tests/host/distinct_host_check.cpp share it.
+// pgx_java_hash_codes), pgx_distinct.cpp (the per-group union), pgx_fasthll.cpp (the decode of a serialized estimator),
+// tests/host/distinct_host_check.cpp and tests/host/fasthll_host_check.cpp share it.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -21,9 +22,10 @@ inline int32_t hash_double(double d) {  // Double.hashCode: (int)(bits ^ bits >>
   if (d == d) std::memcpy(&b, &d, 8);
   return int32_t(uint32_t(b ^ (b >> 32)));
 }
-// String.hashCode over the UTF-16 code units of a UTF-8 string (a malformed byte decodes to U+FFFD)
-inline int32_t hash_utf8(const uint8_t* s, size_t n) {
-  uint32_t h = 0;
+// f(unit) for every UTF-16 code unit of a UTF-8 string, in order (a malformed byte decodes to U+FFFD, a supplementary
+// code point to its surrogate pair)
+template <typename F>
+inline void utf16_units(const uint8_t* s, size_t n, F&& f) {
   for (size_t i = 0; i < n;) {
     uint32_t cp = 0xFFFDu;
     const uint8_t b = s[i];
@@ -43,13 +45,39 @@ inline int32_t hash_utf8(const uint8_t* s, size_t n) {
     ++i;
     if (cp >= 0x10000u) {  // a surrogate pair
       cp -= 0x10000u;
-      h = 31u * h + (0xD800u + (cp >> 10));
-      h = 31u * h + (0xDC00u + (cp & 0x3FFu));
+      f(0xD800u + (cp >> 10));
+      f(0xDC00u + (cp & 0x3FFu));
     } else {
-      h = 31u * h + cp;
+      f(cp);
     }
   }
+}
+// String.hashCode over the UTF-16 code units of a UTF-8 string
+inline int32_t hash_utf8(const uint8_t* s, size_t n) {
+  uint32_t h = 0;
+  utf16_units(s, n, [&](uint32_t unit) { h = 31u * h + unit; });
   return int32_t(h);
+}
+
+// A FASTHLL column's value: HllUtil.convertStringToHll (startree/hll/HllUtil.java: byte = (byte)(char - 129) per UTF-16
+// code unit), then HyperLogLog.Builder.build: big-endian log2m, byte count, and the RegisterSet words of six 5-bit
+// registers (register i: word i / 6, shift 5 * (i % 6)).  regs: 256 bytes.  False for anything but a 180-byte
+// estimator of log2m 8 (the reference throws there: addAll of another size); regs is then not written.
+constexpr int kFastHllChars = 180;  // 8 header bytes and 43 register words (HllUtil.LOG2M_TO_SIZE_IN_BYTES, log2m 8)
+constexpr int kFastHllRegs = 256;
+inline bool fasthll_decode(const uint8_t* s, size_t n, uint8_t* regs) {
+  uint8_t b[kFastHllChars];
+  size_t nb = 0;
+  utf16_units(s, n, [&](uint32_t unit) {
+    if (nb < size_t(kFastHllChars)) b[nb] = uint8_t(unit - 129u);
+    ++nb;
+  });
+  const auto word = [&](int at) {
+    return (uint32_t(b[at]) << 24) | (uint32_t(b[at + 1]) << 16) | (uint32_t(b[at + 2]) << 8) | uint32_t(b[at + 3]);
+  };
+  if (nb != size_t(kFastHllChars) || word(0) != 8u || word(4) != uint32_t(kFastHllChars - 8)) return false;
+  for (int i = 0; i < kFastHllRegs; ++i) regs[i] = uint8_t((word(8 + 4 * (i / 6)) >> (5 * (i % 6))) & 31u);
+  return true;
 }
 
 // out[i] = hashCode of value i.  values: int32 / int64 / float / double per data_type (pgx_data_type: 0..4), or for

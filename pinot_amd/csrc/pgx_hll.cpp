@@ -129,7 +129,9 @@ struct SelDirectory {
 // every selected doc of a multi-value column (DistinctCountHLLMVAggregationFunction.java).  DISTINCTCOUNT and
 // DISTINCTCOUNTMV functions (codes 12, 13) ride the same scan: pgx_distinct.cpp marks their presence bits on the same
 // stream and collects the result's sets afterwards; PERCENTILE and PERCENTILEMV (codes 15, 14) are the third family:
-// pgx_percentile.cpp counts the selected values per dictId and collects the groups' (value, count) pairs.  Planned
+// pgx_percentile.cpp counts the selected values per dictId and collects the groups' (value, count) pairs.  FASTHLL
+// (code 16) is the fourth: presence bitmaps of its own, marked as DISTINCTCOUNT's, whose rows pgx_fasthll.cpp folds
+// through the dictionaries' register images into register blocks that follow the HLL columns' in the result.  Planned
 // afresh every time (no plan cache).
 // With PGX_X_SPARSE_GROUP_SETS a GROUP BY whose key space is not dense or has more than PGX_HLL_MAX_GROUP_SLOTS slots
 // takes the sparse route: the scan runs first (through the global hash table, never the partitioned record path: the
@@ -155,9 +157,21 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   std::vector<char> hmv;           // per HLL column: multi-value (DISTINCTCOUNTHLLMV)
   DistinctRun D;                   // DISTINCTCOUNT / DISTINCTCOUNTMV: their columns, bitmaps and items (pgx_distinct.cpp)
   PercentileRun Q;                 // PERCENTILE / PERCENTILEMV: their columns, counter tables and items (pgx_percentile.cpp)
+  DistinctRun F;                   // FASTHLL: bitmaps as DISTINCTCOUNT's, no hash tables (pgx_fasthll.cpp)
+  F.hashes = false;
+  F.fn = "FASTHLL";
+  std::vector<int> fast_pos(size_t(na), -1);
   for (int a = 0; a < na; ++a) {
     const int f = q.agg_fn[size_t(a)];
-    if (f >= PGX_DISTINCTCOUNTHLL && f <= PGX_PERCENTILE) {
+    if (f == PGX_FASTHLL) {  // (its columns are checked with their dictionaries: fasthll_images)
+      const std::string& c = q.agg_col[size_t(a)];
+      auto it = std::find(F.cols.begin(), F.cols.end(), c);
+      fast_pos[size_t(a)] = int(it - F.cols.begin());
+      if (it == F.cols.end()) {
+        F.cols.push_back(c);
+        F.mv.push_back(0);
+      }
+    } else if (f >= PGX_DISTINCTCOUNTHLL && f <= PGX_PERCENTILE) {
       const std::string& c = q.agg_col[size_t(a)];
       const bool mv = f == PGX_DISTINCTCOUNTHLLMV || f == PGX_DISTINCTCOUNTMV || f == PGX_PERCENTILEMV;
       const bool exact = f == PGX_DISTINCTCOUNT || f == PGX_DISTINCTCOUNTMV;
@@ -192,7 +206,11 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     qs.agg_fn.push_back(PGX_COUNT);
     qs.agg_col.push_back("");
   }
-  const size_t nh = hcols.size();
+  const size_t nh = hcols.size(), nf = F.cols.size();
+  for (int a = 0; a < na; ++a)  // FASTHLL's register blocks follow the HLL columns'
+    if (fast_pos[size_t(a)] >= 0) hll_pos[size_t(a)] = int(nh) + fast_pos[size_t(a)];
+  std::vector<std::vector<const uint32_t*>> fimg;
+  fasthll_images(ctx, segs, n, F, fimg);  // (refuses the columns and the images' bytes before anything runs)
 
   // 1. the rest of the query, with selection bits
   const bool may_sparse = ng > 0 && (xflags & PGX_X_SPARSE_GROUP_SETS) != 0;
@@ -207,6 +225,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   uint64_t slots = ng > 0 && !sparse ? P.dense_slots : 1;  // (a sparse run: the result's groups, known after the scan)
   if (!sparse) {
     distinct_plan(ctx, segs, n, slots, D);  // (refuses tables over PGX_DISTINCT_MAX_TABLE_BYTES before anything runs)
+    distinct_plan(ctx, segs, n, slots, F);  // (FASTHLL's bitmaps count on their own)
     percentile_plan(ctx, segs, n, slots, Q);  // (... over PGX_PERCENTILE_MAX_TABLE_BYTES, and STRING columns)
   } else {
     for (const auto& c : Q.cols)  // (the one refusal of percentile_plan that does not depend on the groups)
@@ -272,12 +291,13 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     SelKeyLayout L;
     if (!sel_key_layout(cards.data(), ng, L))
       fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL under GROUP BY: group keys of more than 128 bits");
-    if (uint64_t(nh) * uint64_t(groups) * kHllRegs * 4 > uint64_t(PGX_HLL_MAX_TABLE_BYTES))
+    if (uint64_t(nh + nf) * uint64_t(groups) * kHllRegs * 4 > uint64_t(PGX_HLL_MAX_TABLE_BYTES))
       fail(PGX_ERR_UNSUPPORTED, "DISTINCTCOUNTHLL: registers over PGX_HLL_MAX_TABLE_BYTES");
     offer = groups > 0;
     if (offer) {
       slots = uint64_t(groups);
       distinct_plan(ctx, segs, n, slots, D);    // (the byte limits, at one row per group)
+      distinct_plan(ctx, segs, n, slots, F);
       percentile_plan(ctx, segs, n, slots, Q);
       // the groups' keys.  One-word keys claim their slot on the key itself and ~0 is the empty slot: a result that
       // holds that key (every field all ones, 64 bits in all) takes two words, where a state word claims the slot
@@ -342,7 +362,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     S.ng = ng;
     S.slots = slots;
     S.sparse = sparse ? &dir.key : nullptr;
-    S.wgs = hll_wgs(ctx, max_words, (nh + D.cols.size() + Q.cols.size()) * size_t(n));
+    S.wgs = hll_wgs(ctx, max_words, (nh + nf + D.cols.size() + Q.cols.size()) * size_t(n));
     S.scanned = scanned;
     S.st = st;
     sel_group_columns(ctx, S);
@@ -365,6 +385,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
                 pgx_launch_hll_offer_group_sparse);
     // the DISTINCTCOUNT[MV] marks, on the same stream
     if (!D.cols.empty()) distinct_mark(ctx, S, D);
+    if (nf) distinct_mark(ctx, S, F);  // FASTHLL: the same marks into its own bitmaps
     // the PERCENTILE[MV] counts, likewise
     if (!Q.cols.empty()) percentile_count(ctx, S, Q);
   }
@@ -381,7 +402,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   // 3. assemble in the request's order; numEntriesScannedPostFilter counts each HLL column among the projected ones
   int extra = 0;  // (a column that functions of several families name counts once)
   std::vector<std::string> special = hcols;
-  for (const auto* cols : {&D.cols, &Q.cols})
+  for (const auto* cols : {&F.cols, &D.cols, &Q.cols})
     for (const auto& c : *cols)
       if (std::find(special.begin(), special.end(), c) == special.end()) special.push_back(c);
   for (const auto& c : special)
@@ -400,13 +421,15 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
   R->pct_pos = pct_pos;
   const int64_t groups = ng > 0 ? Rs.num_groups : 1;
   R->hll_groups = groups;
-  R->hll_regs.assign(nh * size_t(groups) * kHllRegs, 0);
+  R->hll_regs.assign((nh + nf) * size_t(groups) * kHllRegs, 0);
+  uint8_t* const fregs = R->hll_regs.data() + nh * size_t(groups) * kHllRegs;  // FASTHLL's blocks
   if (ng == 0) {
     std::vector<uint32_t> h32(nh * kHllRegs);
     if (nh) hip_check(hipMemcpy(h32.data(), regs.p, h32.size() * 4, hipMemcpyDeviceToHost), "HLL registers D2H");
     for (size_t i = 0; i < h32.size(); ++i) R->hll_regs[i] = uint8_t(h32[i]);
     distinct_collect(ctx, D, std::vector<int64_t>(1, 0), slots, st, R);
     percentile_collect(ctx, Q, std::vector<int64_t>(1, 0), slots, st, R);
+    fasthll_collect(ctx, F, fimg, std::vector<int64_t>(1, 0), slots, st, fregs);
     R->agg_value.assign(size_t(na), 0.0);
     R->agg_count.assign(size_t(na), 0);
     for (int a = 0; a < na; ++a)
@@ -450,6 +473,7 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
     if (gslot[size_t(i)] < 0 || uint64_t(gslot[size_t(i)]) >= slots) fail(PGX_ERR_INTERNAL, "group slot out of range");
   distinct_collect(ctx, D, gslot, slots, st, R);
   percentile_collect(ctx, Q, gslot, slots, st, R);
+  fasthll_collect(ctx, F, fimg, gslot, slots, st, fregs);
   if (nh == 0) return;
   // (a sparse run of more than 65,536 groups goes through pgx_hll_narrow in stretches, each a table of its own read
   // with the first entries of sdev: that rests on gslot[i] == i, checked here as the other two collectors check it)

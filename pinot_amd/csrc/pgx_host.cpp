@@ -1514,6 +1514,7 @@ void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign) {
   for (const StagedColumn& c : seg.cols) {
     auto& k = ctx->col_kinds[c.name];
     (c.is_mv ? k.second : k.first) += sign;
+    if (!c.is_mv && c.data_type == PGX_STRING) k.sv_string += sign;
     if (k.first <= 0 && k.second <= 0) ctx->col_kinds.erase(c.name);
   }
 }
@@ -1632,7 +1633,7 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* d, pgx_query** 
     auto q = std::make_unique<pgx_query>();
     for (int a = 0; a < d->num_aggs; ++a) {
       const int fn = d->aggs[a].fn;
-      if (fn < PGX_COUNT || fn > PGX_PERCENTILE) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
+      if (fn < PGX_COUNT || fn > PGX_FASTHLL) fail(PGX_ERR_UNSUPPORTED, "aggregation function not on the GPU path");
       q->agg_fn.push_back(fn);
       const char* c = d->aggs[a].column;
       std::string col = (c && std::strcmp(c, "*") != 0) ? c : "";
@@ -1649,6 +1650,12 @@ pgx_status pgx_query_compile(pgx_ctx* ctx, const pgx_query_desc* d, pgx_query** 
         if (it != ctx->col_kinds.end() && it->second.first == 0 && it->second.second > 0)
           fail(PGX_ERR_UNSUPPORTED,
                std::string(fn == PGX_PERCENTILE ? "PERCENTILE" : "DISTINCTCOUNT") + " on multi-value column " + col);
+      }
+      if (fn == PGX_FASTHLL) {  // likewise: multi-value or not STRING wherever it is staged
+        std::lock_guard<std::mutex> g(ctx->kinds_mu);
+        auto it = ctx->col_kinds.find(col);
+        if (it != ctx->col_kinds.end() && it->second.sv_string == 0)
+          fail(PGX_ERR_UNSUPPORTED, "FASTHLL needs a single-value STRING column: " + col);
       }
       q->agg_col.push_back(fn == PGX_COUNT ? "" : col);
     }

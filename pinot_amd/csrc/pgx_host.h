@@ -155,6 +155,10 @@ extern "C" hipError_t pgx_launch_distinct_emit(const uint32_t* table, int32_t ca
                                                const int64_t* off, int64_t nrows, int64_t slots, const int32_t* hash,
                                                int32_t* out, int64_t capacity, int wgs_per_row, int wgs,
                                                hipStream_t stream);
+extern "C" int pgx_fasthll_fold_split(int32_t card);
+extern "C" hipError_t pgx_launch_fasthll_fold(const uint32_t* table, int32_t card, const uint32_t* image,
+                                              const int64_t* rows, const int64_t* check, int64_t nrows, int64_t slots,
+                                              uint32_t* out, int wgs, hipStream_t stream);
 extern "C" hipError_t pgx_launch_percentile_count(const pgx::PercentileItem* items, const pgx::PercentileItem* check,
                                                   int nitems, int wgs_per_item, hipStream_t stream);
 extern "C" hipError_t pgx_launch_percentile_count_group(const pgx::PercentileGroupItem* items,
@@ -443,11 +447,14 @@ struct pgx_ctx {
   // domains, so thousands of segments then read one L2-resident table instead of thousands of private copies.
   std::mutex dict_mu;
   std::unordered_map<uint64_t, std::weak_ptr<SharedDict>> dicts;
-  // Per column name: how many staged segments hold it single-value / multi-value (ctx_count_columns).
-  // pgx_query_compile has no segments to look at; with this it refuses a DISTINCTCOUNTHLLMV whose column every staged
-  // segment holds single-value, which run_hll would refuse at every execution over them.
+  // Per column name: how many staged segments hold it single-value / multi-value (ctx_count_columns), and how many of
+  // the former as STRING.  pgx_query_compile has no segments to look at; with this it refuses a DISTINCTCOUNTHLLMV
+  // whose column every staged segment holds single-value, which run_hll would refuse at every execution over them.
+  struct ColKinds {
+    int first = 0, second = 0, sv_string = 0;
+  };
   std::mutex kinds_mu;
-  std::unordered_map<std::string, std::pair<int, int>> col_kinds;
+  std::unordered_map<std::string, ColKinds> col_kinds;
   WorkerPool pool;           // started lazily (first large query)
   std::once_flag pool_once;
   TaskTeam plan_team;        // batched plans (run_batched), started lazily
@@ -638,6 +645,7 @@ struct StagedColumn {
   int max_mv = 0;
   mutable DevBuf hll_codes;  // STRING columns: the DISTINCTCOUNTHLL code table (numeric: shared->hll_codes)
   mutable DevBuf dist_hash;  // STRING columns: the DISTINCTCOUNT hash codes (numeric: shared->dist_hash)
+  mutable DevBuf fasthll_img;  // STRING columns: the FASTHLL register image, card x 256 bytes (pgx_fasthll.cpp; dict_mu)
 };
 
 inline std::atomic<uint64_t> g_segment_uid{1};
@@ -1227,10 +1235,10 @@ void run_hll(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, 
 inline bool is_standard_mv_fn(int fn) { return fn >= PGX_COUNTMV && fn <= PGX_AVGMV; }
 // A segment was staged (sign +1) or is being released (-1): its columns in ctx->col_kinds.
 void ctx_count_columns(pgx_ctx* ctx, const pgx_segment& seg, int sign);
-// (DISTINCTCOUNT[MV] and PERCENTILE[MV] among them: all six run through run_hll and share its limits)
+// (DISTINCTCOUNT[MV], PERCENTILE[MV] and FASTHLL among them: all seven run through run_hll and share its limits)
 inline bool query_has_hll(const pgx_query& q) {
   for (int fn : q.agg_fn)
-    if (fn >= PGX_DISTINCTCOUNTHLL && fn <= PGX_PERCENTILE) return true;
+    if (fn >= PGX_DISTINCTCOUNTHLL && fn <= PGX_FASTHLL) return true;
   return false;
 }
 
@@ -1372,6 +1380,8 @@ struct DistinctRun {
   std::vector<std::vector<DistinctBitmap>> maps;  // per column
   std::vector<std::vector<int>> map_of;           // per column and segment: its bitmap
   DistinctItems items;                            // the mark kernels' items
+  bool hashes = true;                             // false: FASTHLL's run, whose bitmaps need no hash tables
+  const char* fn = "DISTINCTCOUNT";               // the family's name in the refusals
 };
 const int32_t* distinct_hash_table(pgx_ctx* ctx, const StagedColumn& c);  // pgx_hll.cpp, beside the HLL code tables
 void distinct_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots, DistinctRun& D);
@@ -1397,6 +1407,15 @@ struct PercentileRun {
   PercentileItems items;                           // the count kernels' items
 };
 bool same_dictionary(const StagedColumn& a, const StagedColumn& b);  // pgx_distinct.cpp
+
+// ---- pgx_fasthll.cpp: FASTHLL inside run_hll ---------------------------------------------------------------------
+// F: a DistinctRun of its own (hashes false): bitmaps planned and marked as DISTINCTCOUNT's.  images: per column and
+// bitmap (distinct dictionary) its register image; fasthll_images checks the columns and PGX_FASTHLL_MAX_IMAGE_BYTES
+// before it builds one.  fasthll_collect: regs gets per column rows.size() x 256 bytes, in the result's order.
+void fasthll_images(pgx_ctx* ctx, pgx_segment* const* segs, int n, const DistinctRun& F,
+                    std::vector<std::vector<const uint32_t*>>& images);
+void fasthll_collect(pgx_ctx* ctx, const DistinctRun& F, const std::vector<std::vector<const uint32_t*>>& images,
+                     const std::vector<int64_t>& rows, uint64_t slots, hipStream_t st, uint8_t* regs);
 void percentile_plan(pgx_ctx* ctx, pgx_segment* const* segs, int n, uint64_t slots, PercentileRun& Q);
 void percentile_count(pgx_ctx* ctx, const SelScan& S, PercentileRun& Q);
 // rows: the table row (slot) of every group of the result, in its order

@@ -31,8 +31,8 @@ _FN = {"count": N.PGX_COUNT, "sum": N.PGX_SUM, "min": N.PGX_MIN, "max": N.PGX_MA
        "countmv": N.PGX_COUNTMV, "summv": N.PGX_SUMMV, "minmv": N.PGX_MINMV, "maxmv": N.PGX_MAXMV, "avgmv": N.PGX_AVGMV,
        "distinctcounthll": N.PGX_DISTINCTCOUNTHLL, "distinctcounthllmv": N.PGX_DISTINCTCOUNTHLLMV,
        "distinctcount": N.PGX_DISTINCTCOUNT, "distinctcountmv": N.PGX_DISTINCTCOUNTMV,
-       "percentile": N.PGX_PERCENTILE, "percentilemv": N.PGX_PERCENTILEMV}
-_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # their intermediates are register sets (pgx_result_hll)
+       "percentile": N.PGX_PERCENTILE, "percentilemv": N.PGX_PERCENTILEMV, "fasthll": N.PGX_FASTHLL}
+_HLL_FNS = ("distinctcounthll", "distinctcounthllmv", "fasthll")  # their intermediates are register sets (pgx_result_hll)
 _DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... sets of Java hash codes (pgx_result_distinct)
 _PERCENTILE_FNS = ("percentile", "percentilemv")  # ... (value, count) histograms (pgx_result_percentile)
 

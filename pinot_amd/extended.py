@@ -19,7 +19,10 @@ decomposed on the host into GPU sub-queries the fused scan kernels already run:
 * DISTINCTCOUNTHLL(c) -> a function of the base query itself (PGX_DISTINCTCOUNTHLL: the registers are built on the
   device and read with pgx_result_hll; ``native_hll``), and DISTINCTCOUNTHLLMV(c) likewise (PGX_DISTINCTCOUNTHLLMV:
   every value of every selected doc).  Where the library refuses the shape, or with PGX_HLL_NATIVE=0, the same histogram; intermediate the HyperLogLog registers of the distinct hash codes (operator/aggregation/function/
-  DistinctCountHLLAggregationFunction.java aggregate: hll.offer((int) hash)), which depend only on that set (hll.py).
+  DistinctCountHLLAggregationFunction.java aggregate: hll.offer((int) hash)), which depend only on that set (hll.py);
+* FASTHLL(c) -> a function of the base query itself (PGX_FASTHLL: the selected dictIds' decoded estimators are merged on
+  the device, pgx_fasthll.hip, and read with pgx_result_hll; ``native_fasthll``).  Where the library refuses the shape,
+  or with PGX_FASTHLL_NATIVE=0, the same histogram, whose distinct serialized values are deserialized and merged here.
 
 One histogram sub-query serves every DISTINCTCOUNT / PERCENTILE over the same column.  Statistics are the base query's,
 with numEntriesScannedPostFilter counted over the ORIGINAL projection columns (AggregationOperator.java:93-98).
@@ -45,6 +48,7 @@ from .pql import EXT_FUNCTIONS, EXT_MV_FUNCTIONS
 _HIST_FNS = ("distinctcount", "distinctcounthll", "fasthll")
 _NATIVE_HLL_FNS = ("distinctcounthll", "distinctcounthllmv")  # functions of the base query when `native_hll`
 _NATIVE_DISTINCT_FNS = ("distinctcount", "distinctcountmv")  # ... when `native_distinct`
+_NATIVE_FASTHLL_FNS = ("fasthll",)  # ... when `native_fasthll`
 # ... when `native_percentile`: everything reduced from the value histogram of one column
 _NATIVE_PERCENTILE_FNS = tuple("percentile%s%d%s" % (e, p, m) for e in ("", "est") for p in (50, 90, 95, 99)
                                for m in ("", "mv")) + ("minmaxrangemv",)
@@ -183,6 +187,17 @@ def native_percentile(request: dict, segments) -> bool:
     return not _star_tree_request(request, segments)
 
 
+def native_fasthll(request: dict, segments) -> bool:
+    """Whether the request's FASTHLL functions run inside the base query (PGX_FASTHLL, pgx_fasthll.hip), by
+    ``native_hll``'s rules: PGX_FASTHLL_NATIVE=0 forces the histogram, and a request whose base query a star tree could
+    answer keeps the decomposition."""
+    if os.environ.get("PGX_FASTHLL_NATIVE", "1") == "0":
+        return False
+    if not any(a["fn"] in _NATIVE_FASTHLL_FNS for a in request["aggregations"]):
+        return False
+    return not _star_tree_request(request, segments)
+
+
 def sparse_sets_flag() -> int:
     """The execution flag of a group-by base query that holds native functions (``native_hll``, ``native_distinct``,
     ``native_percentile``): PGX_X_SPARSE_GROUP_SETS, with which the library also takes key spaces that are not dense or
@@ -211,8 +226,8 @@ def _from_native_histogram(fn: str, h):
 
 def _base_request(request: dict, native: Sequence[str] = ()):
     """The base GPU request (COUNT(*), the standard functions, MIN + MAX for each MINMAXRANGE, and the functions named
-    in `native`: DISTINCTCOUNTHLL[MV], DISTINCTCOUNT[MV], and one PERCENTILE[MV] per column for the functions reduced
-    from its value histogram) and, per original function, its base slot: an index, a (min, max) index pair,
+    in `native`: DISTINCTCOUNTHLL[MV], DISTINCTCOUNT[MV], FASTHLL, and one PERCENTILE[MV] per column for the functions
+    reduced from its value histogram) and, per original function, its base slot: an index, a (min, max) index pair,
     ("hist", index) for a native value histogram, or None (histogram sub-query functions)."""
     base = [{"fn": "count", "column": "*"}]
     slot = []
@@ -334,7 +349,7 @@ def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -
             return _hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, []))
         if fn == "distinctcounthll" and s is None:
             return HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]].get(key, [])))
-        if fn == "fasthll":
+        if fn == "fasthll" and s is None:
             return _fast_hll(hists[a["column"]].get(key, []))
         if fn.startswith("percentileest"):
             return QD.from_histogram(_numeric(hists[a["column"]].get(key, [])))
@@ -364,10 +379,12 @@ def _run_group_by(ctx, request, segments, combine, native: Sequence[str] = ()) -
 def run(ctx: E.Context, request: dict, segments: Sequence[E.IndexSegment],
         combine: bool = True) -> E.IntermediateResultsBlock:
     """Native where the library takes the shape: first with every enabled family in the base query, then without the
+    FASTHLL family (a refused FASTHLL leaves the others on the routes they take without it), then without the
     percentile family, then with the HLL functions alone (an HLL function keeps its native path when a DISTINCTCOUNT
     beside it is refused), then the full decomposition.  No measured shape ran slower natively than decomposed
-    (tools/bench_percentile.py), so none is routed away beforehand."""
-    families = [(native_percentile(request, segments), _NATIVE_PERCENTILE_FNS),
+    (tools/bench_percentile.py, tools/bench_fasthll.py), so none is routed away beforehand."""
+    families = [(native_fasthll(request, segments), _NATIVE_FASTHLL_FNS),
+                (native_percentile(request, segments), _NATIVE_PERCENTILE_FNS),
                 (native_distinct(request, segments), _NATIVE_DISTINCT_FNS),
                 (native_hll(request, segments), _NATIVE_HLL_FNS)]
     routes = []
@@ -422,7 +439,7 @@ def _run(ctx, request, segments, combine, native) -> E.IntermediateResultsBlock:
             out.append(_hash_set(_dtype(segments, a["column"]), hists[a["column"]]))
         elif fn == "distinctcounthll" and s is None:
             out.append(HLL.from_ints(_hash_set(_dtype(segments, a["column"]), hists[a["column"]])))
-        elif fn == "fasthll":
+        elif fn == "fasthll" and s is None:
             out.append(_fast_hll(hists[a["column"]]))
         elif fn.startswith("percentileest"):  # QuantileDigest of the selected values (pinot_amd/qdigest.py)
             out.append(QD.from_histogram(_numeric(hists[a["column"]])))

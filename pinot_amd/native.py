@@ -25,9 +25,11 @@ PGX_DISTINCTCOUNT = 12
 PGX_DISTINCTCOUNTMV = 13
 PGX_PERCENTILEMV = 14  # the multi-value form has the lower code (pgx.h)
 PGX_PERCENTILE = 15
+PGX_FASTHLL = 16
 PGX_HLL_MAX_GROUP_SLOTS = 65536
 PGX_DISTINCT_MAX_TABLE_BYTES = 256 << 20
 PGX_PERCENTILE_MAX_TABLE_BYTES = 256 << 20
+PGX_FASTHLL_MAX_IMAGE_BYTES = 256 << 20
 PGX_PRED = {"EQ": 0, "NEQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 PGX_F_LEAF, PGX_F_AND, PGX_F_OR = 0, 1, 2
 PGX_MEM_HOST, PGX_MEM_DEVICE = 0, 1
@@ -194,6 +196,7 @@ EXPORTS = {
     "pgx_result_percentile": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_int64]),
     "pgx_histogram_percentile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "pgx_fasthll_registers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "pgx_timing_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]),
 }
 
