@@ -475,7 +475,10 @@ constexpr int kNarrowMaxBits2 = 10;  // second split (pgx_narrow_split): up to 1
 //                      scan units), pf2 (narrow scans load two tiles ahead), noimg (no LDS value images in the query
 //                      kernels), head=N (a lone replay's first part is 1/N of the segments); A/B switches of the sparse
 //                      tile body: densebody (doc-mask filters run the dense row loop), sparsek=N (a wave
-//                      walks set bits while no lane holds more than N selected rows of a sub-step; default kSparseK)
+//                      walks set bits while no lane holds more than N selected rows of a sub-step; default kSparseK).
+//                      Two more are read by pgx_launch_roaring_program_wave itself at every launch, because the tests
+//                      call that launcher without a context: rnarrow (the wave kernel's two-byte container
+//                      reader instead of the wide one), rparts=N (N waves per segment)
 // and, outside the query: PGX_PLAN_CACHE=0 (process-wide), PGX_JIT_CACHE=<dir> / PGX_JIT_DUMP=<dir> (the compiler).
 enum RProgKind { RPROG_AUTO = -1, RPROG_OFF = 0, RPROG_WAVE = 1, RPROG_SEG = 2, RPROG_CHUNK = 3, RPROG_STACK = 4 };
 struct Knobs {

@@ -15,7 +15,11 @@
 #define PGX_J_MAX_RLEAVES 8  // leaves of one bitmap program (== kRProgMaxLeaves)
 struct JRDesc {
   unsigned int* mask;            // separate-expansion path only: nchunks x 2048 words
-  const unsigned char* inv;      // device copy of <col>.bitmap.inv: (card + 1) big-endian int offsets, then the bitmaps
+  const unsigned char* inv;      // device copy of <col>.bitmap.inv: (card + 1) big-endian int offsets, then the bitmaps.
+                                 // Read contract: a container load touches only naturally aligned granules of at most
+                                 // 16 bytes that overlap the container's own bytes, so the buffer must be readable from
+                                 // the 16-byte boundary at or below inv up to the next one past the file's last byte
+                                 // (the staging allocates inv_len + 16 at an aligned base)
   const unsigned int* ids;       // dictIds of the roaring bitmaps to OR (bitmap id starts at inv + BE int at inv + 4 id;
                                  // shared by every segment with the same binding)
   int nb;                        // number of bitmaps

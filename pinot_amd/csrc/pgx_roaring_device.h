@@ -8,7 +8,8 @@
 // without run containers: cookie 12346, container count, (key, card - 1) u16 pairs, u32 offsets, then array (<= 4096
 // u16 values) or bitmap (1024 u64 LE words) containers.  The doc mask of a 65536-doc chunk is 2048 words in LDS: array
 // containers go in bit by bit with LDS atomics, bitmap containers word by word.  Roaring bytes are only 2-byte aligned
-// inside the inverted-index file, so multi-byte fields are read as u16 pairs.
+// inside the inverted-index file, so multi-byte fields are read as u16 pairs (the headers everywhere, and the containers
+// in the workgroup kernels below; the wave kernel of pgx_roaring.hip reads containers as wide aligned granules).
 #ifndef PGX_ROARING_DEVICE_H_
 #define PGX_ROARING_DEVICE_H_
 
@@ -44,23 +45,25 @@ __device__ __forceinline__ int pgx_rcontainer(const unsigned char* base, int chu
   return (int)pgx_rd16(base + 8 + 4 * found + 2) + 1;
 }
 
-// Cursor over one bitmap's containers for kernels that walk a segment's chunks in order: key / card / ptr() describe
-// the first container not yet consumed (key 1 << 30 past the last).  advance() loads the next container's fields at
-// once; they are consumed at a later chunk, so the loads stay in flight while the current container is expanded.
+// Cursor over one bitmap's containers for kernels that walk a segment's chunks in order: key() / card() / ptr()
+// describe the first container not yet consumed (key 1 << 30 past the last).  advance() loads the next container's
+// fields at once; they are consumed at a later chunk, so the loads stay in flight while the current container is
+// expanded.  The loaded words are kept as they come and taken apart in key() / card(): any arithmetic on them inside
+// load() would make advance() wait for its own loads.
 struct PgxRCursor {
   const unsigned char* base = nullptr;
-  int n = 0, cur = 0, key = 1 << 30, card = 0;
-  u32 off = 0;
+  int n = 0, cur = 0;
+  u32 kc = 0, off = 0;  // kc: key | (cardinality - 1) << 16
   __device__ __forceinline__ void load() {
-    int k = 1 << 30, c = card;  // through locals: conditional stores to the members would put the cursor in scratch
-    u32 o = off;
+    u32 k = kc, o = off;  // through locals: conditional stores to the members would put the cursor in scratch
     if (cur < n) {
-      k = (int)pgx_rd16(base + 8 + 4 * cur);
-      c = (int)pgx_rd16(base + 8 + 4 * cur + 2) + 1;
+      k = pgx_rd32(base + 8 + 4 * cur);
       o = pgx_rd32(base + 8 + 4 * n + 4 * cur);
     }
-    key = k, card = c, off = o;
+    kc = k, off = o;
   }
+  __device__ __forceinline__ int key() const { return cur < n ? (int)(kc & 0xFFFFu) : 1 << 30; }
+  __device__ __forceinline__ int card() const { return (int)(kc >> 16) + 1; }
   // first container with key >= c0: keys are strictly increasing, so key[c0] == c0 settles it
   __device__ __forceinline__ void seek(const unsigned char* bitmap, int c0) {
     base = bitmap;
