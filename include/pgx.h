@@ -233,8 +233,18 @@ pgx_status pgx_query_release(pgx_query* q);
  * PGX_SEL_MAX_ROWS, a multi-value column among the order or selected columns, pgx_execute_multi, key domains, dense
  * outputs, pgx_execute_timed.  Selection runs never use a star tree (every raw row is ranked).  The data schema is
  * that of SelectionOperatorUtils.extractDataSchema: the order columns in ORDER BY order, then the selected columns
- * sorted by name, minus those already present; "*" is the first segment's columns. */
+ * sorted by name, minus those already present; "*" is the first segment's columns.
+ * Multi-value columns: only with PGX_Q_SELECT_MV in flags, by which the caller declares that it reads them through
+ * pgx_result_select_kinds / _mv_offsets / _mv_values (pgx_result_select_rows has one int per column and row; without the
+ * flag every status and message is as above).  With it a multi-value column may be among the selected columns, also
+ * through "*" (SelectionFetcher's *ArraySelectionColumnIterator; the reference types it <TYPE>_ARRAY), and among the
+ * ORDER BY columns: there it is a schema column like any order column but no part of the key, per segment or in the
+ * caller's merge (CompositeDocIdValComparator.java:40-44, SelectionOperatorService.getComparator).  The limits of 8
+ * order columns and 64 key bits then count the single-value order columns only, and one of them must remain:
+ * PGX_ERR_UNSUPPORTED "ORDER BY multi-value columns only" otherwise (the reference returns whatever its heap leaves).
+ * A column that is multi-value in one segment of the call and single-value in another: PGX_ERR_UNSUPPORTED. */
 #define PGX_SEL_MAX_ROWS 2048
+#define PGX_Q_SELECT_MV 0x2u /* pgx_select_desc.flags: the caller reads multi-value columns (pgx_result_select_mv_*) */
 typedef struct {
   const char* column;
   int32_t ascending;
@@ -258,10 +268,19 @@ pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* desc, pgx_que
  * group accessors do on a selection result.
  * schema: *num_columns, and names[c] (may be NULL; the strings live as long as the result).
  * counts: rows_per_segment[n].  rows: the segments' rows back to back (total = sum of the counts): seg_index[row],
- * doc_id[row], dict_ids[c * total + row] for schema column c.  Any output may be NULL. */
+ * doc_id[row], dict_ids[c * total + row] for schema column c (a multi-value column: the row's value count).  Any output
+ * may be NULL.
+ * kinds: is_mv[c] per schema column, 1 for a multi-value column (PGX_Q_SELECT_MV), else 0.
+ * mv_offsets / mv_values, for a multi-value schema column (PGX_ERR_INVALID_ARG for a single-value one): over the same
+ * row order as rows, offsets[total + 1]: row j owns values [offsets[j], offsets[j + 1]) of dict_ids[offsets[total]],
+ * the values' dictIds in the doc's own value order (as FixedBitMultiValueReader yields them).  numEntriesScannedPostFilter
+ * stays numDocsScanned x schema size (MSelectionOrderByOperator.java:103). */
 pgx_status pgx_result_select_schema(const pgx_result* r, int32_t* num_columns, const char** names);
 pgx_status pgx_result_select_counts(const pgx_result* r, int32_t* rows_per_segment);
 pgx_status pgx_result_select_rows(const pgx_result* r, int32_t* seg_index, int32_t* doc_id, int32_t* dict_ids);
+pgx_status pgx_result_select_kinds(const pgx_result* r, int32_t* is_mv);
+pgx_status pgx_result_select_mv_offsets(const pgx_result* r, int32_t column, int64_t* offsets);
+pgx_status pgx_result_select_mv_values(const pgx_result* r, int32_t column, int32_t* dict_ids);
 
 /* Per-(segment, leaf) predicate in dictionary-id space, as produced by the caller's PredicateEvaluator:
  * a doc matches iff its dictId d satisfies  (words ? bit d of words : lo <= d <= hi).

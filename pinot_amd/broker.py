@@ -19,7 +19,9 @@ core/query/reduce/BrokerReduceService.java:62-256).  Here:
 * Selection requests with ORDER BY: the server's response carries the combined rows under their data schema; the reduce
   merges all servers' rows with ``SelectionOperatorService.reduceWithOrdering`` (the value comparator over the order
   columns, offset + size rows kept) and renders them with ``renderSelectionResultsWithOrdering`` / ``getFormattedRow``
-  (query/selection/SelectionOperatorService.java:270-301, SelectionOperatorUtils.java:263-330).
+  (query/selection/SelectionOperatorService.java:270-301, SelectionOperatorUtils.java:263-330).  A multi-value
+  column's cell (<TYPE>_ARRAY) is the list of its values, rendered value by value; as an order column it takes no part
+  in the merge.
 """
 from __future__ import annotations
 
@@ -169,6 +171,14 @@ def format_selection_value(data_type: str, v) -> str:
     return java_decimal_format(float(v), 1, 5 if data_type == "FLOAT" else 10)
 
 
+def format_selection_cell(data_type: str, v):
+    """One cell of a rendered selection row (SelectionOperatorUtils.getFormattedRow:263-333): a single-value column's
+    formatted value; a multi-value column's (<TYPE>_ARRAY) list of its values, each formatted as the element type."""
+    if data_type.endswith("_ARRAY"):
+        return [format_selection_value(data_type[:-len("_ARRAY")], x) for x in v]
+    return format_selection_value(data_type, v)
+
+
 @dataclass
 class InstanceResponse:
     """One server's answer (the DataTable's content): aggregation intermediates, trimmed group-by maps, or the
@@ -304,7 +314,7 @@ class BrokerReduceService:
         rows = E.merge_selection_rows(lists, types, sel["order_by"], sel["offset"] + sel["size"])[sel["offset"]:]
         cols = sorted(names) if sel["columns"] == ["*"] else list(sel["columns"])
         idx = [list(names).index(c) for c in cols]
-        return SelectionResults(cols, [[format_selection_value(types[i], row[i]) for i in idx] for row, _ in rows])
+        return SelectionResults(cols, [[format_selection_cell(types[i], row[i]) for i in idx] for row, _ in rows])
 
     @staticmethod
     def _reduce_group_by(broker_request: dict, responses: List[InstanceResponse]) -> List[AggregationResult]:

@@ -123,6 +123,15 @@ extern "C" hipError_t pgx_launch_select_merge(int nitems, int K, int wgs_per_ite
 extern "C" hipError_t pgx_launch_select_gather(const pgx::SelGatherCol* cols, int nitems, int ncols, int K,
                                                const int32_t* out_doc, const int32_t* out_cnt, int32_t* out_ids,
                                                hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_mv_offsets(const pgx::SelMvCol* cols, int nitems, int nmv, int K,
+                                                   const int32_t* out_doc, const int32_t* out_cnt, int32_t* rel_off,
+                                                   int32_t* totals, hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_mv_bases(const int32_t* totals, int64_t npairs, int64_t* bases,
+                                                 hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_mv_gather(const pgx::SelMvCol* cols, int nitems, int nmv, int K,
+                                                  int wgs_per_pair, const int32_t* out_doc, const int32_t* out_cnt,
+                                                  const int32_t* rel_off, const int64_t* bases, int32_t* values,
+                                                  int64_t capacity, hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx::HllItem* check, int nitems,
                                            int wgs_per_item, hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
@@ -837,7 +846,12 @@ struct pgx_result {
   bool select = false;
   std::vector<std::string> sel_schema;
   std::vector<int32_t> sel_counts, sel_seg, sel_doc;
-  std::vector<int32_t> sel_ids;  // [schema column][row]
+  std::vector<int32_t> sel_ids;  // [schema column][row]; a multi-value column's entry is the row's value count
+  // multi-value schema columns (PGX_Q_SELECT_MV): which they are, and per such column the rows' value ranges
+  // (rows + 1 offsets) and the values' dictIds in row order; empty for a single-value column
+  std::vector<int32_t> sel_kinds;
+  std::vector<std::vector<int64_t>> sel_mv_off;
+  std::vector<std::vector<int32_t>> sel_mv_val;
   // DISTINCTCOUNTHLL (run_hll): per function its register block (-1: a standard function), the number of groups
   // (1 for an aggregation-only result) and the registers, [block][group][256]
   std::vector<int> hll_pos;

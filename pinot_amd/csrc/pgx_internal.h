@@ -201,6 +201,12 @@ struct SelGatherCol {          // one schema column of one item (pgx_select_gath
   int32_t bits;
   int32_t pad;
 };
+struct SelMvCol {              // one multi-value schema column of one item (pgx_select_mv_*): pair (column m, item i)
+  const uint32_t* values;      // at [m * nitems + i].  The fixed-bit value stream, padded past its last value
+  const int32_t* start;        // doc d owns values [start[d], start[d + 1]); num_docs + 1 entries
+  int32_t bits;
+  int32_t pad;
+};
 
 // DISTINCTCOUNTHLL (pgx_hll.hip; DistinctCountHLLAggregationFunction over stream-lib's HyperLogLog(log2m = 8)): one
 // item per (segment, function).  codes[dictId] = register << 8 | rank of offer((int) hashCode(value)); the registers

@@ -2,7 +2,8 @@
 // Replaces operator/MSelectionOrderByOperator.java over query/selection/SelectionOperatorService.java (a PriorityQueue of
 // offset + size docs per segment under CompositeDocIdValComparator).  The library returns every segment's best rows as
 // (docId, dictIds); the caller merges the segments' lists by value, where MCombineOperator / SelectionOperatorService
-// .mergeWithOrdering sit in the reference: dictIds of different segments do not compare.
+// .mergeWithOrdering sit in the reference: dictIds of different segments do not compare.  With PGX_Q_SELECT_MV a
+// multi-value schema column returns per row the dictIds of all the doc's values (pgx_select_mv_*, pgx_select.hip).
 // Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
 #include "pgx_host.h"
 
@@ -36,19 +37,27 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   const std::vector<std::string> schema = select_schema(q, n > 0 ? segs[0] : nullptr);
   const int nc = int(schema.size());
 
-  // per-segment key layout and column views
+  // Multi-value columns only for a caller that reads them through pgx_result_select_mv_* (PGX_Q_SELECT_MV).  Among the
+  // order columns one is a schema column like any other but no part of the key (CompositeDocIdValComparator.java:
+  // 40-44 and SelectionOperatorService.getComparator skip it).
+  const bool mv_ok = (q.flags & PGX_Q_SELECT_MV) != 0;
+
+  // per-segment key layout; which schema columns are multi-value (every segment must agree)
   std::vector<SelItem> items(size_t(std::max(n, 0)));
-  std::vector<SelGatherCol> gcols(size_t(std::max(n, 0)) * size_t(nc));
+  std::vector<int32_t> kinds(size_t(nc), 0);
   for (int s = 0; s < n; ++s) {
     SelItem& it = items[size_t(s)];
     it = SelItem{};
     it.num_docs = segs[s]->total_docs;
-    it.ncols = no;
-    int total_bits = 0;
+    int total_bits = 0, nk = 0;
     for (int c = 0; c < no; ++c) {
       const StagedColumn& col = segs[s]->col(q.order_cols[size_t(c)]);
-      if (col.is_mv) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value column " + col.name);
-      SelCol& k = it.c[c];
+      if (col.is_mv) {
+        if (!mv_ok) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value column " + col.name);
+        continue;
+      }
+      if (nk == kSelMaxOrderCols) fail(PGX_ERR_UNSUPPORTED, "more than 8 ORDER BY columns");
+      SelCol& k = it.c[nk++];
       k.fwd = col.fwd;
       k.bits = col.bits;
       k.kbits = bits_for(col.card);
@@ -56,11 +65,32 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
       k.desc = q.order_asc[size_t(c)] ? 0 : 1;
       total_bits += k.kbits;
     }
+    if (nk == 0) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value columns only");
+    it.ncols = nk;
     if (total_bits > 64) fail(PGX_ERR_UNSUPPORTED, "selection order key wider than 64 bits");
     for (int c = 0; c < nc; ++c) {
       const StagedColumn& col = segs[s]->col(schema[size_t(c)]);
-      if (col.is_mv) fail(PGX_ERR_UNSUPPORTED, "selection of multi-value column " + col.name);
-      gcols[size_t(s) * nc + c] = SelGatherCol{col.fwd, col.bits, 0};
+      if (col.is_mv && !mv_ok) fail(PGX_ERR_UNSUPPORTED, "selection of multi-value column " + col.name);
+      if (s == 0) kinds[size_t(c)] = col.is_mv ? 1 : 0;
+      else if (kinds[size_t(c)] != (col.is_mv ? 1 : 0))
+        fail(PGX_ERR_UNSUPPORTED, "column " + col.name + " is multi-value in one segment and single-value in another");
+    }
+  }
+  // column views: the single-value schema columns for pgx_select_gather (a multi-value column's fwd is a value stream,
+  // not one entry per doc: it never goes there), the multi-value ones for pgx_select_mv_*
+  std::vector<int> svi, mvi;
+  for (int c = 0; c < nc; ++c) (kinds[size_t(c)] ? mvi : svi).push_back(c);
+  const int nsv = int(svi.size()), nmv = int(mvi.size());
+  std::vector<SelGatherCol> gcols(size_t(std::max(n, 0)) * size_t(nsv));
+  std::vector<SelMvCol> mcols(size_t(std::max(n, 0)) * size_t(nmv));
+  for (int s = 0; s < n; ++s) {
+    for (int k = 0; k < nsv; ++k) {
+      const StagedColumn& col = segs[s]->col(schema[size_t(svi[size_t(k)])]);
+      gcols[size_t(s) * nsv + k] = SelGatherCol{col.fwd, col.bits, 0};
+    }
+    for (int m = 0; m < nmv; ++m) {
+      const StagedColumn& col = segs[s]->col(schema[size_t(mvi[size_t(m)])]);
+      mcols[size_t(m) * n + s] = SelMvCol{col.fwd, col.mv_start.as<const int32_t>(), col.bits, 0};
     }
   }
 
@@ -72,12 +102,16 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   R->sel_seg.clear();
   R->sel_doc.clear();
   R->sel_ids.clear();
+  R->sel_kinds = kinds;
+  R->sel_mv_off.assign(size_t(nc), {});
+  R->sel_mv_val.assign(size_t(nc), {});
+  for (int c : mvi) R->sel_mv_off[size_t(c)].assign(1, 0);
   if (n == 0) return;
 
   // 1. the filter as COUNT(*): statistics and one selection bit per scanned row
   pgx_query qs = q;
   qs.select = false;
-  qs.flags |= PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
+  qs.flags = (qs.flags & ~PGX_Q_SELECT_MV) | PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
   qs.agg_fn.assign(1, PGX_COUNT);
   qs.agg_col.assign(1, "");
   qs.group_cols.clear();
@@ -128,7 +162,7 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   const size_t rows = size_t(n) * size_t(K);
   DevBuf idev(ctx, items.size() * sizeof(SelItem)), gdev(ctx, std::max<size_t>(1, gcols.size()) * sizeof(SelGatherCol));
   DevBuf ckey(ctx, slots * K * 8), cdoc(ctx, slots * K * 4), ccnt(ctx, slots * 4);
-  DevBuf odoc(ctx, rows * 4), ocnt(ctx, size_t(n) * 4), oids(ctx, std::max<size_t>(1, rows * nc) * 4);
+  DevBuf odoc(ctx, rows * 4), ocnt(ctx, size_t(n) * 4), oids(ctx, std::max<size_t>(1, rows * nsv) * 4);
   hip_check(hipMemcpyAsync(idev.p, items.data(), items.size() * sizeof(SelItem), hipMemcpyHostToDevice, st),
             "selection items H2D");
   if (!gcols.empty())
@@ -143,15 +177,55 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
                                      odoc.as<int32_t>(), ocnt.as<int32_t>(), st),
              "selection merge");
   PGX_LAUNCH(st, "pgx_select_gather",
-             pgx_launch_select_gather(gdev.as<SelGatherCol>(), n, nc, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+             pgx_launch_select_gather(gdev.as<SelGatherCol>(), n, nsv, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
                                       oids.as<int32_t>(), st),
              "selection gather");
   const size_t nseg = size_t(n);
-  std::vector<int32_t> hdoc(rows), hcnt(nseg), hids(rows * nc);
+  std::vector<int32_t> hdoc(rows), hcnt(nseg), hids(rows * nsv);
   hip_check(hipMemcpyAsync(hcnt.data(), ocnt.p, hcnt.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
   hip_check(hipMemcpyAsync(hdoc.data(), odoc.p, hdoc.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
   if (!hids.empty())
     hip_check(hipMemcpyAsync(hids.data(), oids.p, hids.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+
+  // 2b. multi-value schema columns: per pair (column, segment) the rows' value offsets, the pairs' bases, the values.
+  // The value buffer has the grand total's size, read back (8 bytes) between the second and the third launch: the
+  // bound known beforehand, sum over pairs of min(K * max_mv, total_entries), is K times one long doc's length per
+  // pair, and the total is needed on the host anyway before the values are copied.
+  const size_t pairs = nseg * size_t(nmv);
+  std::vector<int32_t> hrel(pairs * size_t(K + 1)), hval;
+  std::vector<int64_t> hbase(pairs + 1, 0);
+  DevBuf mdev, mrel, mtot, mbase, mval;
+  if (nmv > 0) {
+    mdev = DevBuf(ctx, pairs * sizeof(SelMvCol));
+    mrel = DevBuf(ctx, hrel.size() * 4);
+    mtot = DevBuf(ctx, pairs * 4);
+    mbase = DevBuf(ctx, hbase.size() * 8);
+    hip_check(hipMemcpyAsync(mdev.p, mcols.data(), pairs * sizeof(SelMvCol), hipMemcpyHostToDevice, st),
+              "selection multi-value columns H2D");
+    PGX_LAUNCH(st, "pgx_select_mv_offsets",
+               pgx_launch_select_mv_offsets(mdev.as<SelMvCol>(), n, nmv, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+                                            mrel.as<int32_t>(), mtot.as<int32_t>(), st),
+               "selection multi-value offsets");
+    PGX_LAUNCH(st, "pgx_select_mv_bases",
+               pgx_launch_select_mv_bases(mtot.as<int32_t>(), int64_t(pairs), mbase.as<int64_t>(), st),
+               "selection multi-value bases");
+    hip_check(hipMemcpyAsync(hbase.data(), mbase.p, hbase.size() * 8, hipMemcpyDeviceToHost, st), "selection D2H");
+    hip_check(hipMemcpyAsync(hrel.data(), mrel.p, hrel.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    const int64_t grand = hbase[pairs];
+    if (grand < 0) fail(PGX_ERR_INTERNAL, "selection value count out of range");
+    if (grand > 0) {
+      hval.assign(size_t(grand), 0);
+      mval = DevBuf(ctx, size_t(grand) * 4);
+      // workgroups per pair: one per 2048 values of an average pair (each loads the pair's K + 1 offsets first)
+      const int wgs = int(std::min<int64_t>(64, std::max<int64_t>(1, (grand / int64_t(pairs) + 2047) / 2048)));
+      PGX_LAUNCH(st, "pgx_select_mv_gather",
+                 pgx_launch_select_mv_gather(mdev.as<SelMvCol>(), n, nmv, K, wgs, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+                                             mrel.as<int32_t>(), mbase.as<int64_t>(), mval.as<int32_t>(), grand, st),
+                 "selection multi-value gather");
+      hip_check(hipMemcpyAsync(hval.data(), mval.p, hval.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+    }
+  }
   pgx_result Rs;
   finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream
 
@@ -174,9 +248,30 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
     for (int r = 0; r < hcnt[size_t(s)]; ++r, ++at) {
       R->sel_seg.push_back(s);
       R->sel_doc.push_back(hdoc[size_t(s) * K + r]);
-      for (int c = 0; c < nc; ++c)
-        R->sel_ids[size_t(c) * size_t(total) + size_t(at)] = hids[(size_t(c) * n + s) * K + r];
+      for (int k = 0; k < nsv; ++k)
+        R->sel_ids[size_t(svi[size_t(k)]) * size_t(total) + size_t(at)] = hids[(size_t(k) * n + s) * K + r];
     }
+  // a multi-value column's pairs lie back to back in segment order, as its rows do: its values are one stretch of the
+  // value buffer, and a row's offsets are its pair's shifted by the pair's base inside the column
+  for (int m = 0; m < nmv; ++m) {
+    const size_t c = size_t(mvi[size_t(m)]), p0 = size_t(m) * nseg;
+    std::vector<int64_t>& off = R->sel_mv_off[c];
+    off.assign(size_t(total) + 1, 0);
+    const int64_t first = hbase[p0], last = hbase[p0 + nseg];
+    if (first < 0 || last < first || last > int64_t(hval.size()))
+      fail(PGX_ERR_INTERNAL, "selection value offsets out of range");
+    at = 0;
+    for (int s = 0; s < n; ++s) {
+      const int32_t* rel = &hrel[(p0 + size_t(s)) * size_t(K + 1)];
+      const int64_t base = hbase[p0 + size_t(s)] - first;
+      for (int r = 0; r < hcnt[size_t(s)]; ++r, ++at) {
+        off[size_t(at)] = base + rel[r];
+        R->sel_ids[c * size_t(total) + size_t(at)] = rel[r + 1] - rel[r];
+      }
+    }
+    off[size_t(total)] = last - first;
+    R->sel_mv_val[c].assign(hval.begin() + first, hval.begin() + last);
+  }
 }
 
 }  // namespace pgxh
@@ -189,7 +284,9 @@ pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* d, pgx_query*
     if (d->num_columns < 1 || !d->columns) fail(PGX_ERR_INVALID_ARG, "selection without columns");
     if (d->num_order_by < 0 || d->offset < 0 || d->size < 0) fail(PGX_ERR_INVALID_ARG, "negative count");
     if (d->num_order_by == 0) fail(PGX_ERR_UNSUPPORTED, "selection without ORDER BY (MSelectionOnlyOperator)");
-    if (d->num_order_by > kSelMaxOrderCols) fail(PGX_ERR_UNSUPPORTED, "more than 8 ORDER BY columns");
+    // (with PGX_Q_SELECT_MV the limit counts the single-value order columns only: run_select knows which they are)
+    if (d->num_order_by > kSelMaxOrderCols && !(d->flags & PGX_Q_SELECT_MV))
+      fail(PGX_ERR_UNSUPPORTED, "more than 8 ORDER BY columns");
     if (!d->order_by) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     const int64_t rows = int64_t(d->offset) + d->size;
     if (rows == 0) fail(PGX_ERR_UNSUPPORTED, "selection of 0 rows (LIMIT 0)");
@@ -249,6 +346,37 @@ pgx_status pgx_result_select_rows(const pgx_result* r, int32_t* seg_index, int32
     if (seg_index) std::copy(S.sel_seg.begin(), S.sel_seg.end(), seg_index);
     if (doc_id) std::copy(S.sel_doc.begin(), S.sel_doc.end(), doc_id);
     if (dict_ids) std::copy(S.sel_ids.begin(), S.sel_ids.end(), dict_ids);
+  });
+}
+
+pgx_status pgx_result_select_kinds(const pgx_result* r, int32_t* is_mv) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    if (!is_mv) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    std::copy(S.sel_kinds.begin(), S.sel_kinds.end(), is_mv);
+  });
+}
+
+static size_t select_mv_column(const pgx_result& S, int32_t column) {
+  if (column < 0 || size_t(column) >= S.sel_kinds.size() || !S.sel_kinds[size_t(column)])
+    fail(PGX_ERR_INVALID_ARG, "not a multi-value schema column");
+  return size_t(column);
+}
+
+pgx_status pgx_result_select_mv_offsets(const pgx_result* r, int32_t column, int64_t* offsets) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    const auto& off = S.sel_mv_off[select_mv_column(S, column)];
+    if (!offsets) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    std::copy(off.begin(), off.end(), offsets);
+  });
+}
+
+pgx_status pgx_result_select_mv_values(const pgx_result* r, int32_t column, int32_t* dict_ids) {
+  return guarded([&] {
+    const pgx_result& S = select_result(r);
+    const auto& val = S.sel_mv_val[select_mv_column(S, column)];
+    if (dict_ids) std::copy(val.begin(), val.end(), dict_ids);
   });
 }
 

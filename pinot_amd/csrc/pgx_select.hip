@@ -17,6 +17,15 @@
 //   pgx_select_merge   one workgroup per item: the same buffer over the item's candidate lists; writes the final <= K
 //                      docIds best first and their count.
 //   pgx_select_gather  one thread per (schema column, item, rank): the selected doc's dictId.
+//
+// Multi-value schema columns (SelectionFetcher's *ArraySelectionColumnIterator: every value of the doc, in the doc's
+// own order) take three more launches after the merge, over the pairs (multi-value column m, item i) = m * nitems + i:
+//   pgx_select_mv_offsets  one workgroup per pair: the value counts start[d + 1] - start[d] of the item's <= K docs,
+//                          scanned exclusively into K + 1 offsets relative to the pair, and the pair's total.
+//   pgx_select_mv_bases    one workgroup: the exclusive scan of the pairs' totals into int64 bases and the grand total.
+//   pgx_select_mv_gather   one or several workgroups per pair, the pair's offsets in LDS: one output value per thread
+//                          and step -- the thread finds the value's rank by binary search, reads the value from the
+//                          doc's range of the stream and stores it at base + j (consecutive threads, consecutive j).
 // No workgroup waits on another; all stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
@@ -326,6 +335,131 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_gather(const SelGatherCo
   out_ids[idx] = static_cast<int32_t>(pgx_fwd_value(col.fwd, out_doc[row], col.bits));
 }
 
+// ---- multi-value schema columns ---------------------------------------------------------------------------------------
+// Exclusive prefix sum of one value per thread over the workgroup (scan: kSelBlock entries of LDS, free again on
+// return); total: the sum of all.  Called by every thread.
+template <class T>
+__device__ __forceinline__ T sel_block_scan(T v, T* scan, T& total) {
+  const int tid = static_cast<int>(threadIdx.x);
+  scan[tid] = v;
+  __syncthreads();
+  for (int d = 1; d < kSelBlock; d <<= 1) {
+    const T add = tid >= d ? scan[tid - d] : T(0);
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+  total = scan[kSelBlock - 1];
+  const T incl = scan[tid];
+  __syncthreads();
+  return incl - v;
+}
+
+constexpr int kSelMvRanks = 8;  // ranks per thread of pgx_select_mv_offsets: K <= 2048 = 8 * kSelBlock
+
+// The item's row count as the merge wrote it, kept inside [0, K]: no rank past it is ever read as a doc.
+__device__ __forceinline__ int sel_mv_count(const int32_t* __restrict__ out_cnt, int item, int K) {
+  const int c = out_cnt[item];
+  return c < 0 ? 0 : (c > K ? K : c);
+}
+
+__global__ void __launch_bounds__(kSelBlock) pgx_select_mv_offsets(const SelMvCol* __restrict__ cols, int nitems, int nmv,
+                                                                   int K, const int32_t* __restrict__ out_doc,
+                                                                   const int32_t* __restrict__ out_cnt,
+                                                                   int32_t* __restrict__ rel_off,
+                                                                   int32_t* __restrict__ totals) {
+  const int64_t pair = static_cast<int64_t>(blockIdx.x);
+  if (pair >= static_cast<int64_t>(nitems) * nmv) return;
+  __shared__ int32_t scan[kSelBlock];
+  const int tid = static_cast<int>(threadIdx.x);
+  const int item = static_cast<int>(pair % nitems);
+  const int32_t* __restrict__ start = cols[pair].start;
+  const int cnt = sel_mv_count(out_cnt, item, K);
+  // thread t owns the ranks t * E ... t * E + E - 1: one scan over the threads' sums serves all K ranks
+  const int E = (K + kSelBlock - 1) / kSelBlock;
+  int32_t len[kSelMvRanks];
+  int32_t sum = 0;
+#pragma unroll
+  for (int i = 0; i < kSelMvRanks; ++i) {
+    const int r = tid * E + i;
+    len[i] = 0;
+    if (i < E && r < cnt) {
+      const int32_t d = out_doc[static_cast<int64_t>(item) * K + r];
+      len[i] = start[d + 1] - start[d];
+    }
+    sum += len[i];
+  }
+  int32_t total;
+  int32_t at = sel_block_scan<int32_t>(sum, scan, total);
+  int32_t* __restrict__ off = rel_off + pair * (K + 1);
+#pragma unroll
+  for (int i = 0; i < kSelMvRanks; ++i) {
+    const int r = tid * E + i;
+    if (i < E && r < K) off[r] = at;  // ranks at or past the count hold the total: they own no value
+    at += len[i];
+  }
+  if (tid == 0) {
+    off[K] = total;
+    totals[pair] = total;
+  }
+}
+
+__global__ void __launch_bounds__(kSelBlock) pgx_select_mv_bases(const int32_t* __restrict__ totals, int64_t npairs,
+                                                                 int64_t* __restrict__ bases) {
+  if (blockIdx.x != 0) return;
+  __shared__ int64_t scan[kSelBlock];
+  const int tid = static_cast<int>(threadIdx.x);
+  int64_t carry = 0;
+  for (int64_t i0 = 0; i0 < npairs; i0 += kSelBlock) {
+    const int64_t i = i0 + tid;
+    const int64_t v = i < npairs ? totals[i] : 0;
+    int64_t step;
+    const int64_t at = sel_block_scan<int64_t>(v, scan, step);
+    if (i < npairs) bases[i] = carry + at;
+    carry += step;
+  }
+  if (tid == 0) bases[npairs] = carry;
+}
+
+__global__ void __launch_bounds__(kSelBlock) pgx_select_mv_gather(const SelMvCol* __restrict__ cols, int nitems, int nmv,
+                                                                  int K, int G, const int32_t* __restrict__ out_doc,
+                                                                  const int32_t* __restrict__ out_cnt,
+                                                                  const int32_t* __restrict__ rel_off,
+                                                                  const int64_t* __restrict__ bases,
+                                                                  int32_t* __restrict__ values, int64_t capacity) {
+  extern __shared__ int32_t sel_mv_smem[];  // off[K + 1], then per rank start[doc] - off[rank]
+  const int64_t pair = static_cast<int64_t>(blockIdx.x) / G;
+  const int wg = static_cast<int>(static_cast<int64_t>(blockIdx.x) % G);
+  if (pair >= static_cast<int64_t>(nitems) * nmv) return;
+  const int tid = static_cast<int>(threadIdx.x);
+  const int32_t* __restrict__ goff = rel_off + pair * (K + 1);
+  const int32_t total = goff[K];
+  if (static_cast<int64_t>(wg) * kSelBlock >= total) return;  // the whole workgroup: nothing of the pair is left for it
+  const int item = static_cast<int>(pair % nitems);
+  const SelMvCol col = cols[pair];
+  const int cnt = sel_mv_count(out_cnt, item, K);
+  int32_t* off = sel_mv_smem;
+  int32_t* delta = sel_mv_smem + K + 1;
+  for (int r = tid; r <= K; r += kSelBlock) {
+    const int32_t o = goff[r];
+    off[r] = o;
+    if (r < K) delta[r] = r < cnt ? col.start[out_doc[static_cast<int64_t>(item) * K + r]] - o : 0;
+  }
+  __syncthreads();
+  const int64_t base = bases[pair];
+  for (int64_t j = static_cast<int64_t>(wg) * kSelBlock + tid; j < total; j += static_cast<int64_t>(G) * kSelBlock) {
+    // the rank that owns value j: the last r with off[r] <= j (off[0] = 0 <= j < total = off[K]; a doc without
+    // values shares its offset with the next rank and is passed over)
+    int lo = 0, hi = K;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= j) lo = mid; else hi = mid;
+    }
+    if (base + j < capacity)
+      values[base + j] = static_cast<int32_t>(pgx_fwd_value2(col.values, static_cast<int64_t>(delta[lo]) + j, col.bits));
+  }
+}
+
 }  // namespace pgx
 
 // LDS entries of the candidate buffer for K rows: a power of two (bitonic sort) with room for K kept entries plus one
@@ -378,5 +512,50 @@ extern "C" hipError_t pgx_launch_select_gather(const pgx::SelGatherCol* cols, in
   if (blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pgx::pgx_select_gather, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kSelBlock), 0, stream, cols,
                      nitems, ncols, K, out_doc, out_cnt, out_ids);
+  return hipGetLastError();
+}
+
+// The multi-value launches run after pgx_launch_select_merge on its stream, over out_doc / out_cnt as it wrote them.
+// cols holds nmv x nitems descriptors, pair (multi-value column m, item i) at [m * nitems + i].
+static bool sel_mv_args_ok(int nitems, int nmv, int K) {
+  return sel_args_ok(nitems, K, 1) && nmv >= 0 && static_cast<int64_t>(nitems) * nmv <= 0x7FFFFFFF / 64;
+}
+
+// rel_off holds (K + 1) int32 per pair: rank r of the pair owns values [rel_off[r], rel_off[r + 1]) of the pair's
+// values, ranks at or past the item's count none; totals one int32 per pair (= its rel_off[K]).
+extern "C" hipError_t pgx_launch_select_mv_offsets(const pgx::SelMvCol* cols, int nitems, int nmv, int K,
+                                                   const int32_t* out_doc, const int32_t* out_cnt, int32_t* rel_off,
+                                                   int32_t* totals, hipStream_t stream) {
+  if (!sel_mv_args_ok(nitems, nmv, K) || !cols || !out_doc || !out_cnt || !rel_off || !totals)
+    return hipErrorInvalidValue;
+  const int64_t pairs = static_cast<int64_t>(nitems) * nmv;
+  if (pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_select_mv_offsets, dim3(static_cast<unsigned>(pairs)), dim3(pgx::kSelBlock), 0, stream,
+                     cols, nitems, nmv, K, out_doc, out_cnt, rel_off, totals);
+  return hipGetLastError();
+}
+
+// bases holds npairs + 1 int64: where each pair's values start in the value buffer, and the grand total.
+extern "C" hipError_t pgx_launch_select_mv_bases(const int32_t* totals, int64_t npairs, int64_t* bases,
+                                                 hipStream_t stream) {
+  if (npairs < 0 || npairs > 0x7FFFFFFF / 64 || (npairs > 0 && !totals) || !bases) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pgx::pgx_select_mv_bases, dim3(1), dim3(pgx::kSelBlock), 0, stream, totals, npairs, bases);
+  return hipGetLastError();
+}
+
+// values holds `capacity` dictIds (the grand total of pgx_launch_select_mv_bases, or more): pair p's value j at
+// [bases[p] + j]; nothing is stored at or past capacity.  wgs_per_pair workgroups share a pair's values.
+extern "C" hipError_t pgx_launch_select_mv_gather(const pgx::SelMvCol* cols, int nitems, int nmv, int K,
+                                                  int wgs_per_pair, const int32_t* out_doc, const int32_t* out_cnt,
+                                                  const int32_t* rel_off, const int64_t* bases, int32_t* values,
+                                                  int64_t capacity, hipStream_t stream) {
+  if (!sel_mv_args_ok(nitems, nmv, K) || wgs_per_pair < 1 || wgs_per_pair > 64 || capacity < 0 || !cols || !out_doc ||
+      !out_cnt || !rel_off || !bases || (capacity > 0 && !values))
+    return hipErrorInvalidValue;
+  const int64_t pairs = static_cast<int64_t>(nitems) * nmv;
+  if (pairs == 0 || capacity == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_select_mv_gather, dim3(static_cast<unsigned>(pairs * wgs_per_pair)), dim3(pgx::kSelBlock),
+                     size_t(2 * K + 1) * 4, stream, cols, nitems, nmv, K, wgs_per_pair, out_doc, out_cnt, rel_off, bases,
+                     values, capacity);
   return hipGetLastError();
 }

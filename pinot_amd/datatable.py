@@ -24,8 +24,9 @@ sum / min / max, OBJECT for the rest) and getAggregationGroupByResultDataTable (
 name, OBJECT HashMap<group string, intermediate>), then attachMetadataToDataTable (numDocsScanned,
 numEntriesScannedInFilter, numEntriesScannedPostFilter, totalDocs, "Exception<code>" entries).  A selection response is
 the rows under their data schema (SelectionOperatorUtils.getDataTableFromRowSet, query/selection/SelectionOperatorUtils
-.java: one INT / LONG / FLOAT / DOUBLE / STRING cell per single-value column); no reference fixture pins these bytes,
-they are checked by round trip only.  Java HashMap iteration
+.java: one INT / LONG / FLOAT / DOUBLE / STRING cell per single-value column, one INT_ARRAY / LONG_ARRAY / FLOAT_ARRAY /
+DOUBLE_ARRAY / STRING_ARRAY cell per multi-value column, pointing into the variable-size section); no reference fixture
+pins these bytes, the array cells included: they are checked by round trip only.  Java HashMap iteration
 order (the order the reference writes map entries and metadata) is reproduced for String keys: buckets of
 (h ^ h >>> 16) & (capacity - 1) over String.hashCode at the capacity a default HashMap grows to, entries of one bucket
 in insertion order.  IntOpenHashSet's order is fastutil's internal table order in the reference and ascending here;
@@ -44,7 +45,14 @@ HEADER_BYTES = 52
 
 # FieldSpec.DataType names used by DataSchema (common/data/FieldSpec.java:209-228) and fixed cell widths
 CELL_BYTES = {"BOOLEAN": 1, "BYTE": 1, "CHAR": 2, "SHORT": 2, "INT": 4, "LONG": 8, "FLOAT": 8, "DOUBLE": 8,
-              "STRING": 4, "OBJECT": 8}
+              "STRING": 4, "OBJECT": 8,
+              "INT_ARRAY": 8, "LONG_ARRAY": 8, "FLOAT_ARRAY": 8, "DOUBLE_ARRAY": 8, "STRING_ARRAY": 8}
+
+# Array cells (a multi-value column of a selection; DataTableBuilder.setColumn(int, int[] | long[] | float[] | double[] |
+# String[]), :396-477, read by DataTable.get*Array, DataTable.java:673-742): the fixed cell is (position in the
+# variable-size section, number of elements), the elements lie there back to back in these formats -- a float element is
+# 4 bytes, where a FLOAT cell is a double; a String element is its id in the column's dictionary.
+ARRAY_ELEMENT = {"INT_ARRAY": "i", "LONG_ARRAY": "q", "FLOAT_ARRAY": "f", "DOUBLE_ARRAY": "d", "STRING_ARRAY": "i"}
 
 # DataTableSerDe.DataType ids (common/utils/DataTableSerDe.java:30-41)
 T_OBJECT, T_STRING, T_MUTABLE_LONG, T_DOUBLE, T_DOUBLE_ARRAY, T_AVG_PAIR, T_MIN_MAX_RANGE, T_HLL, T_QDIGEST, \
@@ -244,6 +252,14 @@ class DataTable:
                     if self.version == V2:
                         var += _i32(object_type(v))
                     var += ob
+                elif t in ARRAY_ELEMENT:
+                    if t == "STRING_ARRAY":
+                        ids = dictionary.setdefault(self.columns[c], {})
+                        for x in v:
+                            ids.setdefault(x, len(ids))
+                        v = [ids[x] for x in v]
+                    struct.pack_into(">ii", cell, o, len(var), len(v))
+                    var += struct.pack(">%d%s" % (len(v), ARRAY_ELEMENT[t]), *v)
                 else:
                     raise ValueError("cell type %s not supported" % t)
             fixed += cell
@@ -351,6 +367,10 @@ class DataTable:
                         row.append(deserialize_object(var[start + 4:start + 4 + ln], typ))
                     else:
                         raise ValueError("version-1 DataTables hold Java-serialized objects: not read")
+                elif t in ARRAY_ELEMENT:
+                    start, n = struct.unpack_from(">ii", fixed, o)
+                    vals = list(struct.unpack_from(">%d%s" % (n, ARRAY_ELEMENT[t]), var, start))
+                    row.append([rev[dt.columns[c]][i] for i in vals] if t == "STRING_ARRAY" else vals)
                 else:
                     raise ValueError("cell type %s not supported" % t)
             dt.rows.append(row)

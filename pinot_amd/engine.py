@@ -18,6 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import math
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -236,6 +237,8 @@ class IndexSegment:
             d.bits_per_element = c.bits
             d.is_sorted = 0
             d.dict_width = c.dict_width
+            d.is_multi_value = int(c.is_mv)  # (fwd: the whole <col>.mv.fwd, as for a host segment)
+            d.total_entries = c.total_entries
             d.fwd = C.c_void_p(fwd_device[name][0])
             d.fwd_len = fwd_device[name][1]
             p = (dict_device or {}).get(name)
@@ -599,10 +602,20 @@ class _Query:
             pass
 
 
+def select_mv_flag() -> int:
+    """The flag of a selection query's descriptor: PGX_Q_SELECT_MV, with which the library also takes multi-value
+    columns among the selected and the ORDER BY columns (``decode_selection`` reads them through
+    pgx_result_select_mv_*).  The flag is passed only with PGX_SELECT_MV_NATIVE=1 (read here, at every request).
+    Without it such a selection is refused as before the flag: the plan maker's refusal is pinned by
+    tests/test_gpu_select.py, so the route through the plan maker is opt-in, as it is at the ABI."""
+    return N.PGX_Q_SELECT_MV if os.environ.get("PGX_SELECT_MV_NATIVE", "0") == "1" else 0
+
+
 class _SelectQuery(_Query):
     """A compiled selection query (pgx_select_compile) for one broker request with "selections"."""
 
-    def __init__(self, ctx: Context, request: dict):
+    def __init__(self, ctx: Context, request: dict, flags: Optional[int] = None):
+        """flags: the descriptor's PGX_Q_* flags; None: what the environment asks for (select_mv_flag)."""
         self.ctx = ctx
         self.request = request
         sel = request["selections"]
@@ -627,7 +640,7 @@ class _SelectQuery(_Query):
             larr[i].column = lkeep[i]
             larr[i].kind = N.PGX_PRED[lf["op"]]
         sd = N.SelectDesc(len(cols), carr, len(self.order_by), oarr, self.offset, self.size, len(nodes), narr,
-                          len(leaves), larr, 0)
+                          len(leaves), larr, select_mv_flag() if flags is None else flags)
         self._keep = [cols, carr, oarr, okeep, narr, larr, lkeep]
         h = C.c_void_p()
         N.check(N.lib().pgx_select_compile(ctx.handle, C.byref(sd), C.byref(h)))
@@ -661,11 +674,14 @@ def merge_selection_rows(lists, types, order_by, limit):
     getComparator: the first len(order_by) schema columns, each ascending or descending), down to `limit` rows, best
     first.  lists: per segment (or server) a list of (row values in schema order, (segment index, docId)); ties of
     the whole key go by (segment index, docId) -- this project's tie rule, where the reference's PriorityQueue keeps
-    whichever its heap order leaves."""
+    whichever its heap order leaves.  An order column of an _ARRAY type (a multi-value column) takes no part, as
+    getComparator leaves it out (its switch's `default: break`)."""
     import functools
 
     def cmp(x, y):
         for i, o in enumerate(order_by):
+            if types[i].endswith("_ARRAY"):
+                continue
             r = _java_compare(types[i], x[0][i], y[0][i])
             if r:
                 return r if o["asc"] else -r
@@ -694,12 +710,27 @@ def decode_selection(q: _SelectQuery, r, segments: Sequence[IndexSegment]):
     ids = np.zeros(max(1, total * len(cols)), np.int32)
     N.check(L.pgx_result_select_rows(r, seg.ctypes.data, doc.ctypes.data, ids.ctypes.data))
     ids = ids[:total * len(cols)].reshape(len(cols), total)
-    types = [segments[0].column(c).meta.data_type for c in cols] if segments else []
+    # multi-value schema columns (PGX_Q_SELECT_MV): typed <TYPE>_ARRAY as extractDataSchema does, the cell the list of
+    # the doc's values in value order
+    kinds = np.zeros(max(1, len(cols)), np.int32)
+    N.check(L.pgx_result_select_kinds(r, kinds.ctypes.data))
+    mv = {}
+    for c in range(len(cols)):
+        if kinds[c]:
+            off = np.zeros(total + 1, np.int64)
+            N.check(L.pgx_result_select_mv_offsets(r, c, off.ctypes.data))
+            val = np.zeros(max(1, int(off[total])), np.int32)
+            N.check(L.pgx_result_select_mv_values(r, c, val.ctypes.data))
+            mv[c] = (off, val)
+    types = [segments[0].column(c).meta.data_type + ("_ARRAY" if kinds[i] else "") for i, c in enumerate(cols)] \
+        if segments else []
     lists = [[] for _ in segments]
     for j in range(total):
         s = int(seg[j])
         infos = [segments[s].column(c) for c in cols]
-        lists[s].append(([_typed_value(ci, int(ids[c, j])) for c, ci in enumerate(infos)], (s, int(doc[j]))))
+        row = [[_typed_value(ci, int(v)) for v in mv[c][1][mv[c][0][j]:mv[c][0][j + 1]]] if c in mv
+               else _typed_value(ci, int(ids[c, j])) for c, ci in enumerate(infos)]
+        lists[s].append((row, (s, int(doc[j]))))
     return ExecutionStatistics(*list(st)), cols, types, lists
 
 

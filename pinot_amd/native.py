@@ -39,6 +39,7 @@ PGX_X_NO_PARTITION = 0x4
 PGX_X_THROUGHPUT = 0x8
 PGX_X_SPARSE_GROUP_SETS = 0x10  # the set functions under GROUP BY over sparse / large key spaces (pgx.h)
 PGX_Q_NO_STAR_TREE = 0x1
+PGX_Q_SELECT_MV = 0x2  # pgx_select_desc.flags: the caller reads multi-value columns through pgx_result_select_mv_*
 ERR_UNSUPPORTED = 2
 PGX_ERR_TIMEOUT = 5
 PGX_ERR_INTERNAL = 6
@@ -139,6 +140,9 @@ EXPORTS = {
     "pgx_result_select_schema": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
     "pgx_result_select_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pgx_result_select_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgx_result_select_kinds": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pgx_result_select_mv_offsets": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "pgx_result_select_mv_values": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "pgx_query_set_key_domain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "pgx_execute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(LeafBinding),

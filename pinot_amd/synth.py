@@ -245,7 +245,9 @@ def padded_fwd_bytes(rows: int, bits: int) -> int:
 class DeviceSegments:
     """Synthetic segments resident in HBM, staged through the C-ABI (pgx_segment_stage with PGX_MEM_DEVICE)."""
 
-    def __init__(self, ctx, wl: Workload, seg_ids: List[int], rows: int = None):
+    def __init__(self, ctx, wl: Workload, seg_ids: List[int], rows: int = None, extra=()):
+        """extra: further columns (segment.Column with fwd_bytes, e.g. a multi-value column's <col>.mv.fwd) that every
+        segment holds with the same content, beside the workload's generated ones."""
         from .engine import IndexSegment
         self.ctx = ctx
         self.wl = wl
@@ -267,6 +269,12 @@ class DeviceSegments:
                 N.check(L.pgx_device_alloc(ctx.handle, len(b), C.byref(p)))
                 N.check(L.pgx_copy_to_device(ctx.handle, p, b, len(b)))
                 shared_bytes[c.name], shared_dev[c.name] = b, p
+        extra_dev = {}
+        for col in extra:  # one device copy of the index for every staging (staging copies it)
+            p = C.c_void_p()
+            N.check(L.pgx_device_alloc(ctx.handle, len(col.fwd_bytes), C.byref(p)))
+            N.check(L.pgx_copy_to_device(ctx.handle, p, col.fwd_bytes, len(col.fwd_bytes)))
+            extra_dev[col.name] = (p, len(col.fwd_bytes))
         for s in self.seg_ids:
             cols = []
             fwd_dev = {}
@@ -300,11 +308,14 @@ class DeviceSegments:
                         np.int64)
                 cols.append(Column(c.name, "DOUBLE" if f64 else "INT", "DIMENSION", c.card, c.bits, self.rows, self.rows,
                                    False, inv_bytes is not None, dict_bytes, 8 if f64 else 4, None, None, inv_bytes))
+            for col in extra:
+                cols.append(col)
+                fwd_dev[col.name] = (extra_dev[col.name][0].value, extra_dev[col.name][1])
             seg = SegmentData("%s_%d" % (wl.name, s), self.rows, self.rows, {c.name: c for c in cols})
             self.segments.append(IndexSegment.from_device(ctx, seg, fwd_dev, shared_dev))
             for col in cols:  # staging copied the index; inv_offsets keeps what algorithmic_bytes reads of it
                 col.inv_bytes = None
-        for p in shared_dev.values():  # staging copied them
+        for p in list(shared_dev.values()) + [p for p, _ in extra_dev.values()]:  # staging copied them
             L.pgx_device_free(ctx.handle, p)
 
     def _inverted_indexes(self):

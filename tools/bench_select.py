@@ -11,7 +11,12 @@ intervals per step), after warm-up:
                 it must decode (the selected ones), over the MI355X's measured HBM copy rate (6.29 TB/s)
 Prints one JSON line per case and writes them all to --out.
 
+--mv adds one multi-value column (10-bit dictIds, 1 .. 5 values per doc, 3 on average, the same content in every
+segment) to the same shape and times, beside each single-value row, the selection that also returns that column
+(PGX_Q_SELECT_MV): its step, the three pgx_select_mv_* launches, and the bytes that cross to the host.
+
   python tools/bench_select.py --out profiles/select/bench_select.json
+  python tools/bench_select.py --mv --out profiles/select_mv/bench_select_mv.json
 """
 import argparse
 import ctypes as C
@@ -24,6 +29,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HBM_BYTES_PER_S = 6.29e12  # MI355X HBM3E as measured by a float4 copy; the spec peak is 8.0 TB/s
 
 
+def mv_column(name, rows, card=1000, seed=5):
+    """A multi-value INT column of `rows` docs in the v1 format (segment.pack_mv_fwd, without a list per doc): doc d
+    holds 1 + d % 5 values, dictIds uniform below card."""
+    import numpy as np
+
+    from pinot_amd import segment as S
+    lens = 1 + np.arange(rows, dtype=np.int64) % 5
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    tv = int(starts[-1])
+    bits = S.num_bits(card)
+    dpc = S.mv_docs_per_chunk(rows, tv)
+    head = starts[np.arange((rows + dpc - 1) // dpc) * dpc].astype(">i4").tobytes()
+    first = np.zeros((tv + 7) // 8 * 8, dtype=np.uint8)
+    first[starts[:-1]] = 1
+    ids = np.random.default_rng(seed).integers(0, card, tv).astype(np.int64)
+    fwd = head + np.packbits(first).tobytes()[:(tv + 7) // 8] + \
+        S.pack_fixed_bit_chunked(ids, bits)[:(tv * bits + 7) // 8]
+    return S.Column(name, "INT", "DIMENSION", card, bits, rows, rows, False, False,
+                    np.arange(card).astype(">i4").tobytes(), 4, fwd, None, None, S.DEFAULT_PAD, True, tv, 5)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segments", type=int, default=64)
@@ -31,6 +57,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mv", action="store_true", help="also select one multi-value column of about 3 values per doc")
     args = ap.parse_args()
 
     from pinot_amd import engine as E
@@ -43,7 +70,8 @@ def main():
     wl = S.Workload("sel", "selection ORDER BY o1, o2 DESC", args.segments, args.rows, cols, "", 9, "weak")
     ctx = E.Context(0)
     L = N.lib()
-    dev = S.DeviceSegments(ctx, wl, list(range(args.segments)), rows=args.rows)
+    dev = S.DeviceSegments(ctx, wl, list(range(args.segments)), rows=args.rows,
+                           extra=[mv_column("mv", args.rows)] if args.mv else ())
     segs = dev.segments
     c5 = " WHERE (f1 IN (%s) OR f2 = 7) AND f3 <> 3" % ",".join(str(v) for v in range(3, 1000, 31)[:32])
     order_bits = sum(c.bits for c in cols if c.name in ("o1", "o2"))
@@ -91,6 +119,27 @@ def main():
                    "topk_over_floor": None if not topk_ms else round(topk_ms / floor_ms, 2),
                    "hbm_bytes_per_s": HBM_BYTES_PER_S, "steps": args.steps, "warmup": args.warmup,
                    "kernels_ms_per_step": {n: round(v, 4) for n, v in sorted(per.items())}}
+            if args.mv:
+                mq = E._SelectQuery(ctx, pql.compile("SELECT f2, mv FROM T%s ORDER BY o1, o2 DESC LIMIT %d" % (flt, k)),
+                                    flags=N.PGX_Q_SELECT_MV)
+                mv_ms, mdetail, mstats = timed(mq)
+                r = mq.execute(segs)
+                _, names, _, lists = E.decode_selection(mq, r, segs)
+                L.pgx_result_release(r)
+                mq.close()
+                assert mstats[:2] == sstats[:2] and names == ["o1", "o2", "f2", "mv"], (mstats, names)
+                nrows = sum(len(x) for x in lists)
+                values = sum(len(rw[0][3]) for x in lists for rw in x)
+                mkern = mdetail.get("kernels", mdetail)
+                mper = {name: v[1] / args.steps for name, v in mkern.items() if isinstance(v, list) and len(v) == 2}
+                # what run_select copies to the host: counts, docIds, the single-value dictIds; per (column, segment) the
+                # K + 1 offsets and a base, the grand total; the selected values
+                row["mv"] = {"select_ms": round(mv_ms, 4), "rows": nrows, "values": values,
+                             "offsets_ms": mper.get("pgx_select_mv_offsets"), "bases_ms": mper.get("pgx_select_mv_bases"),
+                             "gather_ms": mper.get("pgx_select_mv_gather"),
+                             "bytes_returned": args.segments * (4 + k * 4 * 4 + (k + 1) * 4 + 8) + 8 + values * 4,
+                             "bytes_returned_single_value": args.segments * (4 + k * 4 * 4),
+                             "kernels_ms_per_step": {n: round(v, 4) for n, v in sorted(mper.items())}}
             results.append(row)
             print(json.dumps(row), flush=True)
     dev.free()
