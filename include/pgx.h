@@ -242,9 +242,32 @@ pgx_status pgx_query_release(pgx_query* q);
  * caller's merge (CompositeDocIdValComparator.java:40-44, SelectionOperatorService.getComparator).  The limits of 8
  * order columns and 64 key bits then count the single-value order columns only, and one of them must remain:
  * PGX_ERR_UNSUPPORTED "ORDER BY multi-value columns only" otherwise (the reference returns whatever its heap leaves).
- * A column that is multi-value in one segment of the call and single-value in another: PGX_ERR_UNSUPPORTED. */
+ * A column that is multi-value in one segment of the call and single-value in another: PGX_ERR_UNSUPPORTED.
+ * Without ORDER BY (plan/SelectionPlanNode.java:42-47 -> operator/query/MSelectionOnlyOperator.java:58-110): only with
+ * PGX_Q_SELECT_ONLY in flags, by which the caller declares that it merges the segments' lists in call order
+ * (SelectionOperatorUtils.mergeWithoutOrdering) and applies no offset (renderSelectionResultsWithoutOrdering); without
+ * the flag every status and message is as above, and with the flag and num_order_by >= 1 the query is the ORDER BY
+ * query as before.  With it and num_order_by == 0 the result holds per segment its first min(matches, size) docs in
+ * ascending docId (the offset plays no part in what is returned: _limitDocs = size); the schema is the selected columns
+ * sorted by name.  Limits: size >= 1, offset + size <= PGX_SEL_MAX_ROWS (the doc-id operator hands out blocks of
+ * offset + size docs, and the statistics below depend on that block), multi-value selected columns only together with
+ * PGX_Q_SELECT_MV; pgx_execute_multi, key domains, dense outputs and pgx_execute_timed are refused as for ORDER BY.
+ * pgx_result_stats, summed over the segments, with c = min(matches, size) per segment: numDocsScanned = c,
+ * numEntriesScannedPostFilter = c x schema size, numTotalRawDocs = the segment's raw docs, and
+ * numEntriesScannedInFilter = what the filter's iterators had counted when the operator stopped pulling, after
+ * P = offset + size calls of next() on the root (BReusableFilteredDocIdSetOperator.java:68-93) or at its end.  That
+ * number is computed for three classes of filter:
+ *   (a) no scan leaf (no filter, or sorted / bitmap leaves only): 0;
+ *   (b) the whole filter is one scan leaf on a single-value column: docId of the P-th match + 1 in a segment with at
+ *       least P matches, the segment's raw docs otherwise (the scan ran to its end);
+ *   (d) a root AND whose children are all leaves, at least one of them sorted / bitmap: the full run's number, whatever
+ *       P (AndBlockDocIdSet.fastIterator builds its answer before the first next()).
+ * Every other filter (an AND of scan leaves only, any OR with a scan leaf, nested operators over a scan leaf) leaves
+ * its scan iterators in a state that depends on where the pulling stopped: PGX_ERR_UNSUPPORTED at execution, with
+ * "numEntriesScannedInFilter" in the message, also when the segments of one call fall into different classes. */
 #define PGX_SEL_MAX_ROWS 2048
 #define PGX_Q_SELECT_MV 0x2u /* pgx_select_desc.flags: the caller reads multi-value columns (pgx_result_select_mv_*) */
+#define PGX_Q_SELECT_ONLY 0x4u /* pgx_select_desc.flags: num_order_by == 0 is accepted (MSelectionOnlyOperator) */
 typedef struct {
   const char* column;
   int32_t ascending;
@@ -252,7 +275,7 @@ typedef struct {
 typedef struct {
   int32_t num_columns;
   const char* const* columns; /* as written; a single "*" = all columns */
-  int32_t num_order_by;       /* >= 1 */
+  int32_t num_order_by;       /* >= 1; 0 with PGX_Q_SELECT_ONLY */
   const pgx_order_by* order_by;
   int32_t offset, size;       /* LIMIT offset, size */
   int32_t num_filter_nodes;
@@ -264,7 +287,8 @@ typedef struct {
 pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* desc, pgx_query** out);
 /* Selection results: per segment its best <= offset + size rows, best first; the caller merges the segments' lists by
  * value (MCombineOperator -> SelectionOperatorService.mergeWithOrdering in the reference: dictIds of different segments
- * do not compare).  They return PGX_ERR_INVALID_ARG on an aggregation or group-by result, as pgx_result_agg and the
+ * do not compare).  Without ORDER BY (PGX_Q_SELECT_ONLY): per segment its first <= size rows in ascending docId; the
+ * caller appends the segments' lists in call order up to size rows.  They return PGX_ERR_INVALID_ARG on an aggregation or group-by result, as pgx_result_agg and the
  * group accessors do on a selection result.
  * schema: *num_columns, and names[c] (may be NULL; the strings live as long as the result).
  * counts: rows_per_segment[n].  rows: the segments' rows back to back (total = sum of the counts): seg_index[row],

@@ -22,6 +22,9 @@ core/query/reduce/BrokerReduceService.java:62-256).  Here:
   (query/selection/SelectionOperatorService.java:270-301, SelectionOperatorUtils.java:263-330).  A multi-value
   column's cell (<TYPE>_ARRAY) is the list of its values, rendered value by value; as an order column it takes no part
   in the merge.
+* Selection requests without ORDER BY: the reduce appends the servers' rows in the given order up to ``size`` rows
+  (``SelectionOperatorUtils.reduceWithoutOrdering``) and renders them without cutting the offset
+  (``renderSelectionResultsWithoutOrdering``).
 """
 from __future__ import annotations
 
@@ -305,13 +308,18 @@ class BrokerReduceService:
         """SelectionOperatorService.reduceWithOrdering + renderSelectionResultsWithOrdering: the servers' rows merged
         by the value comparator down to offset + size, the first `offset` dropped, best first; the columns in the
         request's order ("*": the schema's columns sorted, getSelectionColumns), every value formatted.  Rows equal
-        in every order column keep the order of the responses and of their rows."""
+        in every order column keep the order of the responses and of their rows.  Without ORDER BY
+        (reduceWithoutOrdering + renderSelectionResultsWithoutOrdering): the responses' rows appended in the given
+        order up to `size` rows, and no offset cut."""
         sel = broker_request["selections"]
-        if not sel["order_by"]:
-            raise ValueError("selection without ORDER BY is not on this path")
         names, types = responses[0].selection_schema
         lists = [[(row, (s, i)) for i, row in enumerate(r.selection)] for s, r in enumerate(responses)]
-        rows = E.merge_selection_rows(lists, types, sel["order_by"], sel["offset"] + sel["size"])[sel["offset"]:]
+        if not sel["order_by"]:
+            # BrokerReduceService.java:182-185 -> SelectionOperatorUtils.reduceWithoutOrdering: the servers in the
+            # given order, their rows in order, up to `size`; renderSelectionResultsWithoutOrdering cuts no offset
+            rows = E.merge_selection_rows_unordered(lists, sel["size"])
+        else:
+            rows = E.merge_selection_rows(lists, types, sel["order_by"], sel["offset"] + sel["size"])[sel["offset"]:]
         cols = sorted(names) if sel["columns"] == ["*"] else list(sel["columns"])
         idx = [list(names).index(c) for c in cols]
         return SelectionResults(cols, [[format_selection_cell(types[i], row[i]) for i in idx] for row, _ in rows])

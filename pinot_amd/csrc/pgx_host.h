@@ -132,6 +132,11 @@ extern "C" hipError_t pgx_launch_select_mv_gather(const pgx::SelMvCol* cols, int
                                                   int wgs_per_pair, const int32_t* out_doc, const int32_t* out_cnt,
                                                   const int32_t* rel_off, const int64_t* bases, int32_t* values,
                                                   int64_t capacity, hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_first_count(const pgx::SelItem* items, int nitems, int K, int wgs_per_item,
+                                                    int32_t* stripe_cnt, hipStream_t stream);
+extern "C" hipError_t pgx_launch_select_first(const pgx::SelItem* items, int nitems, int K, int wgs_per_item,
+                                              const int32_t* stripe_cnt, int32_t* out_doc, int32_t* out_cnt, int limit,
+                                              int32_t* out_lim, hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_offer(const pgx::HllItem* items, const pgx::HllItem* check, int nitems,
                                            int wgs_per_item, hipStream_t stream);
 extern "C" hipError_t pgx_launch_hll_offer_group(const pgx::HllGroupItem* items, const pgx::HllGroupItem* check,
@@ -1192,6 +1197,8 @@ uint64_t initial_hash_cap(pgx_segment* const* segs, int n, const ExecPlan& P);
 void stage_dict(pgx_ctx* ctx, pgx_segment* seg, const std::vector<uint8_t>& dict_host, StagedColumn& c);
 GlobalDict group_dict(const pgx_query& q, pgx_segment* const* segs, int n, int g);
 int reference_mode(const pgx_query& q, const pgx_segment* seg);
+PNode build_tree(const pgx_query& q, const pgx_segment& seg0);  // the physical filter tree over one segment's indexes
+bool has_scan_leaf(const PNode& n);
 void plan_query(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
                 uint32_t xflags, ExecPlan& P, const Domain* dom = nullptr);
 void finish_result(pgx_ctx* ctx, const pgx_query& q, ExecPlan& P, ExecBuffers& B, pgx_segment* const* segs, int n,

@@ -481,7 +481,9 @@ constexpr int kNarrowMaxBits2 = 10;  // second split (pgx_narrow_split): up to 1
 //                      scan units), pf2 (narrow scans load two tiles ahead), noimg (no LDS value images in the query
 //                      kernels), head=N (a lone replay's first part is 1/N of the segments); A/B switches of the sparse
 //                      tile body: densebody (doc-mask filters run the dense row loop), sparsek=N (a wave
-//                      walks set bits while no lane holds more than N selected rows of a sub-step; default kSparseK).
+//                      walks set bits while no lane holds more than N selected rows of a sub-step; default kSparseK);
+//                      of the selection without ORDER BY: firstg=N (N workgroups per segment in
+//                      pgx_select_first, 1 .. 64; default: one).
 //                      Two more are read by pgx_launch_roaring_program_wave itself at every launch, because the tests
 //                      call that launcher without a context: rnarrow (the wave kernel's two-byte container
 //                      reader instead of the wide one), rparts=N (N waves per segment)
@@ -504,6 +506,7 @@ struct Knobs {
   bool narrow_log = false;  // PGX_DEBUG narrow_log
   bool dense_body = false;  // PGX_DEBUG densebody: doc-mask filters run the dense row loop, no sparse tile body (A/B)
   int sparse_k = -1;        // PGX_DEBUG sparsek=N: the sparse body's per-lane row limit (-1: kSparseK) (A/B)
+  int sel_first_g = 0;      // PGX_DEBUG firstg=N: workgroups per segment of pgx_select_first (0: run_select's choice)
   bool host_profile = false;
 };
 Knobs read_knobs();

@@ -292,6 +292,7 @@ Knobs pgx::read_knobs() {
     else if (o == "densebody") k.dense_body = true;
     else if (o.rfind("sparsek=", 0) == 0) k.sparse_k = std::min(32, std::max(0, std::atoi(o.c_str() + 8)));
     else if (o.rfind("head=", 0) == 0) k.lone_head = std::max(2, std::atoi(o.c_str() + 5));
+    else if (o.rfind("firstg=", 0) == 0) k.sel_first_g = std::min(64, std::max(0, std::atoi(o.c_str() + 7)));
     i = j + 1;
   }
   return k;

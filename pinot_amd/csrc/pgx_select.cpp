@@ -4,6 +4,9 @@
 // (docId, dictIds); the caller merges the segments' lists by value, where MCombineOperator / SelectionOperatorService
 // .mergeWithOrdering sit in the reference: dictIds of different segments do not compare.  With PGX_Q_SELECT_MV a
 // multi-value schema column returns per row the dictIds of all the doc's values (pgx_select_mv_*, pgx_select.hip).
+// Without ORDER BY (PGX_Q_SELECT_ONLY; operator/query/MSelectionOnlyOperator.java:58-110) a segment's rows are its first
+// docs in docId order (pgx_select_first), the caller appends the segments' lists in call order, and the operator's early
+// stop changes all four statistics: run_select's `only` branch.
 // Reference paths are relative to pinot-core/src/main/java/com/linkedin/pinot/core/.
 #include "pgx_host.h"
 
@@ -25,6 +28,60 @@ static std::vector<std::string> select_schema(const pgx_query& q, const pgx_segm
   return cols;
 }
 
+// numEntriesScannedInFilter when MSelectionOnlyOperator stops pulling after P = offset + size docs
+// (BReusableFilteredDocIdSetOperator.java:68-93 calls next() on the root P times, or until its end): what the filter's
+// iterators had counted by then.  Closed forms exist for three classes of the physical tree:
+//   'a'  no scan leaf: 0;
+//   'b'  the whole filter is one scan leaf on a single-value column (SVScanDocIdIterator.next counts every row up to
+//        and including each match): docId of the P-th match + 1, or the segment's raw docs when the scan reached its end;
+//   'd'  a root AND whose children are all leaves, at least one of them sorted / bitmap (AndBlockDocIdSet.fastIterator
+//        builds the answer, every scan child's applyAnd included, before the first next()): the full run's number.
+// Any other tree (0) leaves scan iterators in a state that depends on where the pulling stopped: an AND of scans has
+// counted the rows up to the last doc only, an OR's scan children each stand at their own next match.
+static char select_only_class(const PNode& root, const pgx_query& q, const pgx_segment& seg) {
+  if (!has_scan_leaf(root)) return 'a';
+  if (root.op == PGX_F_LEAF) return seg.col(q.leaf_col[size_t(root.leaf)]).is_mv ? 0 : 'b';
+  if (root.op != PGX_F_AND) return 0;
+  bool index = false;
+  for (const PNode& k : root.kids) {
+    if (k.op != PGX_F_LEAF) return 0;
+    index |= k.phys == PH_SORTED || k.phys == PH_BITMAP;
+  }
+  return index ? 'd' : 0;
+}
+
+static void leaf_kinds(const PNode& n, std::vector<int>& phys) {
+  if (n.op == PGX_F_LEAF) phys[size_t(n.leaf)] = n.phys;
+  for (const PNode& k : n.kids) leaf_kinds(k, phys);
+}
+
+// The class of a selection without ORDER BY over all segments of the call; refuses what has no closed form.  plan_query
+// plans the filter with the first segment's index kinds: for class 'd', whose number is the full run's, every segment
+// must agree with it leaf by leaf.
+static char select_only_classify(const pgx_query& q, pgx_segment* const* segs, int n) {
+  if (q.filter.empty()) return 'a';
+  char cls = 0;
+  std::vector<int> phys0;
+  for (int s = 0; s < n; ++s) {
+    const PNode root = build_tree(q, *segs[s]);
+    const char c = select_only_class(root, q, *segs[s]);
+    std::vector<int> phys(q.leaf_col.size(), PH_SCAN);
+    leaf_kinds(root, phys);
+    if (c == 0)
+      fail(PGX_ERR_UNSUPPORTED,
+           "selection without ORDER BY: numEntriesScannedInFilter of this filter depends on where the operator stops "
+           "(closed forms: no scan leaf, one scan leaf, a root AND of leaves with a sorted / bitmap leaf)");
+    if (s == 0) {
+      cls = c;
+      phys0 = phys;
+    } else if (c != cls || (c == 'd' && phys != phys0)) {
+      fail(PGX_ERR_UNSUPPORTED,
+           "selection without ORDER BY: the segments' indexes put numEntriesScannedInFilter into different classes");
+    }
+  }
+  return cls;
+}
+
 void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int n, const pgx_leaf_binding* bindings,
                 const pgx_exec_opts* opts, pgx_result* R, hipStream_t st) {
   const uint32_t xflags = opts ? opts->flags : 0;
@@ -34,6 +91,7 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   if (n < 0 || n > 65535) fail(PGX_ERR_UNSUPPORTED, "selection over more than 65535 segments");
   const int K = q.sel_offset + q.sel_size;
   const int no = int(q.order_cols.size());
+  const bool only = no == 0;  // MSelectionOnlyOperator (pgx_select_compile took it with PGX_Q_SELECT_ONLY)
   const std::vector<std::string> schema = select_schema(q, n > 0 ? segs[0] : nullptr);
   const int nc = int(schema.size());
 
@@ -65,7 +123,7 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
       k.desc = q.order_asc[size_t(c)] ? 0 : 1;
       total_bits += k.kbits;
     }
-    if (nk == 0) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value columns only");
+    if (nk == 0 && !only) fail(PGX_ERR_UNSUPPORTED, "ORDER BY multi-value columns only");
     it.ncols = nk;
     if (total_bits > 64) fail(PGX_ERR_UNSUPPORTED, "selection order key wider than 64 bits");
     for (int c = 0; c < nc; ++c) {
@@ -107,46 +165,53 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   R->sel_mv_val.assign(size_t(nc), {});
   for (int c : mvi) R->sel_mv_off[size_t(c)].assign(1, 0);
   if (n == 0) return;
+  // without ORDER BY: which closed form the filter statistic takes, refused before anything is allocated; a request
+  // without a filter selects every doc (a null mask), launches no query kernel and allocates no mask
+  const char only_class = only ? select_only_classify(q, segs, n) : 0;
+  const bool scan = !only || !q.filter.empty();
 
   // 1. the filter as COUNT(*): statistics and one selection bit per scanned row
   pgx_query qs = q;
   qs.select = false;
-  qs.flags = (qs.flags & ~PGX_Q_SELECT_MV) | PGX_Q_NO_STAR_TREE;  // every raw row gets its selection bit
+  qs.flags = (qs.flags & ~(PGX_Q_SELECT_MV | PGX_Q_SELECT_ONLY)) | PGX_Q_NO_STAR_TREE;  // every raw row gets its bit
   qs.agg_fn.assign(1, PGX_COUNT);
   qs.agg_col.assign(1, "");
   qs.group_cols.clear();
   qs.key_domain.clear();
   ExecPlan P;
-  P.want_selmask = true;
-  plan_query(ctx, qs, segs, n, bindings, xflags, P);
-  P.sel_off.assign(size_t(n), 0);
-  int64_t words = 0;
-  int max_words = 0;
-  for (int s = 0; s < n; ++s) {
-    P.sel_off[size_t(s)] = words;
-    const int w = (P.ksegs[size_t(s)].num_docs + 31) / 32 + 1;
-    words += w;
-    max_words = std::max(max_words, w);
-  }
-  P.sel_buf = DevBuf(ctx, size_t(std::max<int64_t>(words, 1)) * 4);
-  hip_check(hipMemsetAsync(P.sel_buf.p, 0, size_t(std::max<int64_t>(words, 1)) * 4, st), "selection masks");
   ExecBuffers B;
-  upload_plan(ctx, P, B, st);
-  plan_jit(ctx, qs, segs, n, P, B);
-  if (P.jit.empty()) {
-    for (int s = 0; s < n; ++s)
-      if (P.ksegs[size_t(s)].num_docs != 0) fail(PGX_ERR_UNSUPPORTED, "selection queries need the query kernels");
-    R->stats[3] = P.total_raw;  // every segment empty: nothing scanned, no rows
-    return;
+  int max_words = 0;
+  if (scan) {
+    P.want_selmask = true;
+    plan_query(ctx, qs, segs, n, bindings, xflags, P);
+    P.sel_off.assign(size_t(n), 0);
+    int64_t words = 0;
+    for (int s = 0; s < n; ++s) {
+      P.sel_off[size_t(s)] = words;
+      int w = (P.ksegs[size_t(s)].num_docs + 31) / 32 + 1;
+      if (only) w = (w + 3) & ~3;  // pgx_select_first reads 16 bytes per thread: every segment's mask starts aligned
+      words += w;
+      max_words = std::max(max_words, w);
+    }
+    P.sel_buf = DevBuf(ctx, size_t(std::max<int64_t>(words, 1)) * 4);
+    hip_check(hipMemsetAsync(P.sel_buf.p, 0, size_t(std::max<int64_t>(words, 1)) * 4, st), "selection masks");
+    upload_plan(ctx, P, B, st);
+    plan_jit(ctx, qs, segs, n, P, B);
+    if (P.jit.empty()) {
+      for (int s = 0; s < n; ++s)
+        if (P.ksegs[size_t(s)].num_docs != 0) fail(PGX_ERR_UNSUPPORTED, "selection queries need the query kernels");
+      R->stats[3] = P.total_raw;  // every segment empty: nothing scanned, no rows
+      return;
+    }
+    alloc_outputs(ctx, P, B, nullptr, 0);
+    reset_outputs(P, B, st);
+    launch_scan(P, st);
   }
-  alloc_outputs(ctx, P, B, nullptr, 0);
-  reset_outputs(P, B, st);
-  launch_scan(P, st);
 
-  // 2. per-segment top K, merge, gather -- on the same stream
+  // 2. per-segment top K and merge (without ORDER BY: the first K selected docs), gather -- on the same stream
   for (int s = 0; s < n; ++s) {
-    items[size_t(s)].sel = P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)];
-    items[size_t(s)].num_docs = P.ksegs[size_t(s)].num_docs;
+    items[size_t(s)].sel = scan ? P.sel_buf.as<uint32_t>() + P.sel_off[size_t(s)] : nullptr;
+    items[size_t(s)].num_docs = scan ? P.ksegs[size_t(s)].num_docs : segs[s]->total_raw_docs;
   }
   // workgroups per segment: at least 4 steps of 256 mask words each, and no more over all segments than stay resident
   // (8 of 256 threads per CU, fewer when the candidate buffers fill the LDS): the scan hides its load latency with
@@ -158,31 +223,63 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
   int G = std::max(1, (max_words + 4 * kSelBlock - 1) / (4 * kSelBlock));
   G = std::min(G, std::max(1, resident * ctx->num_cus / n));
   G = std::min(G, 64);
+  if (only) {
+    // workgroups per segment of pgx_select_first: at least 4 steps of 256 chunks of 4 mask words each, and no more
+    // over all segments than stay resident (8 of 256 threads per CU).  PGX_DEBUG firstg=N sets the number (A/B runs).
+    G = std::max(1, max_words / (4 * 4 * kSelBlock));
+    G = std::min(G, std::max(1, 8 * ctx->num_cus / n));
+    G = std::min(G, 64);
+    if (q.kn.sel_first_g > 0) G = q.kn.sel_first_g;
+  }
   const size_t slots = size_t(n) * size_t(G);
   const size_t rows = size_t(n) * size_t(K);
+  const size_t nseg = size_t(n);
   DevBuf idev(ctx, items.size() * sizeof(SelItem)), gdev(ctx, std::max<size_t>(1, gcols.size()) * sizeof(SelGatherCol));
-  DevBuf ckey(ctx, slots * K * 8), cdoc(ctx, slots * K * 4), ccnt(ctx, slots * 4);
-  DevBuf odoc(ctx, rows * 4), ocnt(ctx, size_t(n) * 4), oids(ctx, std::max<size_t>(1, rows * nsv) * 4);
+  DevBuf ckey, cdoc, ccnt(ctx, slots * 4);
+  DevBuf odoc(ctx, rows * 4), ocnt(ctx, nseg * 4), oids(ctx, std::max<size_t>(1, rows * nsv) * 4);
   hip_check(hipMemcpyAsync(idev.p, items.data(), items.size() * sizeof(SelItem), hipMemcpyHostToDevice, st),
             "selection items H2D");
   if (!gcols.empty())
     hip_check(hipMemcpyAsync(gdev.p, gcols.data(), gcols.size() * sizeof(SelGatherCol), hipMemcpyHostToDevice, st),
               "selection columns H2D");
-  PGX_LAUNCH(st, "pgx_select_topk",
-             pgx_launch_select_topk(idev.as<SelItem>(), n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(),
-                                    ccnt.as<int32_t>(), st),
-             "selection top-K");
-  PGX_LAUNCH(st, "pgx_select_merge",
-             pgx_launch_select_merge(n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(), ccnt.as<int32_t>(),
-                                     odoc.as<int32_t>(), ocnt.as<int32_t>(), st),
-             "selection merge");
+  // hfound: without ORDER BY, the docs found per segment among the first K = offset + size (the statistics read them);
+  // the rows returned, and everything gathered for them, are the first `size` of those (olim)
+  std::vector<int32_t> hfound;
+  DevBuf olim;
+  const int32_t* rcnt = ocnt.as<int32_t>();  // the row counts the gathers run over
+  if (!only) {
+    ckey = DevBuf(ctx, slots * K * 8);
+    cdoc = DevBuf(ctx, slots * K * 4);
+    PGX_LAUNCH(st, "pgx_select_topk",
+               pgx_launch_select_topk(idev.as<SelItem>(), n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(),
+                                      ccnt.as<int32_t>(), st),
+               "selection top-K");
+    PGX_LAUNCH(st, "pgx_select_merge",
+               pgx_launch_select_merge(n, K, G, ckey.as<uint64_t>(), cdoc.as<uint32_t>(), ccnt.as<int32_t>(),
+                                       odoc.as<int32_t>(), ocnt.as<int32_t>(), st),
+               "selection merge");
+  } else {
+    if (G > 1)
+      PGX_LAUNCH(st, "pgx_select_first_count",
+                 pgx_launch_select_first_count(idev.as<SelItem>(), n, K, G, ccnt.as<int32_t>(), st),
+                 "selection first-K count");
+    if (q.sel_offset > 0) {
+      olim = DevBuf(ctx, nseg * 4);
+      rcnt = olim.as<int32_t>();
+    }
+    PGX_LAUNCH(st, "pgx_select_first",
+               pgx_launch_select_first(idev.as<SelItem>(), n, K, G, ccnt.as<int32_t>(), odoc.as<int32_t>(),
+                                       ocnt.as<int32_t>(), q.sel_size, olim.as<int32_t>(), st),
+               "selection first-K");
+    hfound.assign(nseg, 0);
+    hip_check(hipMemcpyAsync(hfound.data(), ocnt.p, nseg * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+  }
   PGX_LAUNCH(st, "pgx_select_gather",
-             pgx_launch_select_gather(gdev.as<SelGatherCol>(), n, nsv, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
-                                      oids.as<int32_t>(), st),
+             pgx_launch_select_gather(gdev.as<SelGatherCol>(), n, nsv, K, odoc.as<int32_t>(), rcnt, oids.as<int32_t>(),
+                                      st),
              "selection gather");
-  const size_t nseg = size_t(n);
   std::vector<int32_t> hdoc(rows), hcnt(nseg), hids(rows * nsv);
-  hip_check(hipMemcpyAsync(hcnt.data(), ocnt.p, hcnt.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
+  hip_check(hipMemcpyAsync(hcnt.data(), rcnt, hcnt.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
   hip_check(hipMemcpyAsync(hdoc.data(), odoc.p, hdoc.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
   if (!hids.empty())
     hip_check(hipMemcpyAsync(hids.data(), oids.p, hids.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
@@ -203,7 +300,7 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
     hip_check(hipMemcpyAsync(mdev.p, mcols.data(), pairs * sizeof(SelMvCol), hipMemcpyHostToDevice, st),
               "selection multi-value columns H2D");
     PGX_LAUNCH(st, "pgx_select_mv_offsets",
-               pgx_launch_select_mv_offsets(mdev.as<SelMvCol>(), n, nmv, K, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+               pgx_launch_select_mv_offsets(mdev.as<SelMvCol>(), n, nmv, K, odoc.as<int32_t>(), rcnt,
                                             mrel.as<int32_t>(), mtot.as<int32_t>(), st),
                "selection multi-value offsets");
     PGX_LAUNCH(st, "pgx_select_mv_bases",
@@ -220,24 +317,44 @@ void run_select(pgx_ctx* ctx, const pgx_query& q, pgx_segment* const* segs, int 
       // workgroups per pair: one per 2048 values of an average pair (each loads the pair's K + 1 offsets first)
       const int wgs = int(std::min<int64_t>(64, std::max<int64_t>(1, (grand / int64_t(pairs) + 2047) / 2048)));
       PGX_LAUNCH(st, "pgx_select_mv_gather",
-                 pgx_launch_select_mv_gather(mdev.as<SelMvCol>(), n, nmv, K, wgs, odoc.as<int32_t>(), ocnt.as<int32_t>(),
+                 pgx_launch_select_mv_gather(mdev.as<SelMvCol>(), n, nmv, K, wgs, odoc.as<int32_t>(), rcnt,
                                              mrel.as<int32_t>(), mbase.as<int64_t>(), mval.as<int32_t>(), grand, st),
                  "selection multi-value gather");
       hip_check(hipMemcpyAsync(hval.data(), mval.p, hval.size() * 4, hipMemcpyDeviceToHost, st), "selection D2H");
     }
   }
   pgx_result Rs;
-  finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream
+  if (scan) finish_result(ctx, qs, P, B, segs, n, st, &Rs, nullptr);  // waits for the stream
+  else hip_check(hipStreamSynchronize(st), "sync");
 
   // 3. statistics as MSelectionOrderByOperator.getNextBlock reports them; rows compacted segment by segment
-  R->stats[0] = Rs.stats[0];
-  R->stats[1] = Rs.stats[1];
-  R->stats[2] = Rs.stats[0] * nc;
-  R->stats[3] = Rs.stats[3];
   int64_t total = 0;
   for (int s = 0; s < n; ++s) {
     if (hcnt[size_t(s)] < 0 || hcnt[size_t(s)] > K) fail(PGX_ERR_INTERNAL, "selection row count out of range");
     total += hcnt[size_t(s)];
+  }
+  if (!only) {
+    R->stats[0] = Rs.stats[0];
+    R->stats[1] = Rs.stats[1];
+    R->stats[2] = Rs.stats[0] * nc;
+    R->stats[3] = Rs.stats[3];
+  } else {
+    // MSelectionOnlyOperator.java:92-110: the docs it took, times the schema size, and the segment's raw docs; the
+    // filter's entries by the class of select_only_class (a segment with fewer than K matches was pulled to its end:
+    // the full run's number, which for a root scan leaf is the segment's raw docs)
+    int64_t entries = 0, raw = 0;
+    for (int s = 0; s < n; ++s) {
+      const int32_t found = hfound[size_t(s)];
+      if (found < hcnt[size_t(s)] || found > K) fail(PGX_ERR_INTERNAL, "selection row count out of range");
+      const int64_t docs = items[size_t(s)].num_docs;
+      raw += docs;
+      if (only_class == 'b') entries += found == K ? int64_t(hdoc[size_t(s) * K + size_t(K) - 1]) + 1 : docs;
+    }
+    if (only_class == 'd') entries = Rs.stats[1];
+    R->stats[0] = total;
+    R->stats[1] = entries;
+    R->stats[2] = total * nc;
+    R->stats[3] = raw;
   }
   R->sel_counts = hcnt;
   R->sel_seg.reserve(size_t(total));
@@ -283,13 +400,16 @@ pgx_status pgx_select_compile(pgx_ctx* ctx, const pgx_select_desc* d, pgx_query*
     if (!ctx || !d || !out) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     if (d->num_columns < 1 || !d->columns) fail(PGX_ERR_INVALID_ARG, "selection without columns");
     if (d->num_order_by < 0 || d->offset < 0 || d->size < 0) fail(PGX_ERR_INVALID_ARG, "negative count");
-    if (d->num_order_by == 0) fail(PGX_ERR_UNSUPPORTED, "selection without ORDER BY (MSelectionOnlyOperator)");
+    const bool only = d->num_order_by == 0 && (d->flags & PGX_Q_SELECT_ONLY);
+    if (d->num_order_by == 0 && !only) fail(PGX_ERR_UNSUPPORTED, "selection without ORDER BY (MSelectionOnlyOperator)");
     // (with PGX_Q_SELECT_MV the limit counts the single-value order columns only: run_select knows which they are)
     if (d->num_order_by > kSelMaxOrderCols && !(d->flags & PGX_Q_SELECT_MV))
       fail(PGX_ERR_UNSUPPORTED, "more than 8 ORDER BY columns");
-    if (!d->order_by) fail(PGX_ERR_INVALID_ARG, "NULL argument");
+    if (!d->order_by && !only) fail(PGX_ERR_INVALID_ARG, "NULL argument");
     const int64_t rows = int64_t(d->offset) + d->size;
     if (rows == 0) fail(PGX_ERR_UNSUPPORTED, "selection of 0 rows (LIMIT 0)");
+    // (without ORDER BY the offset plays no part in what is returned: MSelectionOnlyOperator's _limitDocs = size)
+    if (only && d->size == 0) fail(PGX_ERR_UNSUPPORTED, "selection of 0 rows (LIMIT 0)");
     if (rows > PGX_SEL_MAX_ROWS) fail(PGX_ERR_UNSUPPORTED, "selection of more than PGX_SEL_MAX_ROWS rows");
     auto q = std::make_unique<pgx_query>();
     q->select = true;

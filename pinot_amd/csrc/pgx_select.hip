@@ -27,6 +27,9 @@
 //                          and step -- the thread finds the value's rank by binary search, reads the value from the
 //                          doc's range of the stream and stores it at base + j (consecutive threads, consecutive j).
 // No workgroup waits on another; all stores are plain vector stores.
+//
+// Selection without ORDER BY (MSelectionOnlyOperator) replaces the top-K and the merge by pgx_select_first_count /
+// pgx_select_first, described where they are defined; the gather and the multi-value launches run unchanged after them.
 #include <hip/hip_runtime.h>
 
 #include "pgx_device.h"
@@ -460,6 +463,190 @@ __global__ void __launch_bounds__(kSelBlock) pgx_select_mv_gather(const SelMvCol
   }
 }
 
+// ---- selection without ORDER BY ---------------------------------------------------------------------------------------
+// MSelectionOnlyOperator (operator/query/MSelectionOnlyOperator.java:58-110) takes the first docs the filter yields, in
+// docId order, and stops: per item the first K set bits of its selection mask.
+//   pgx_select_first_count  grid (G, items), G > 1 only.  Workgroup g owns a contiguous stripe of the item's mask: the
+//                           16-byte chunks (four 32-row words, 128 rows) [g * S, (g + 1) * S), S = ceil(chunks / G).
+//                           It writes the stripe's popcount saturated at K to stripe_cnt[item * G + g], and leaves its
+//                           loop as soon as the running count reaches K.
+//   pgx_select_first        the same grid.  The workgroup's base is the sum of the stripes before its own (one lane per
+//                           stripe, G <= 64); a workgroup whose base is at or past K returns.  Per step every thread
+//                           loads one chunk (one 16-byte load where the mask is 16-byte aligned, else word by word),
+//                           popcounts it, and an exclusive scan inside the wave64 and across the four waves through LDS
+//                           gives it its rank; a thread whose rank is below K writes its set bits' docIds at
+//                           out_doc[item * K + rank ...] while that stays below K.  The loop ends, for the whole
+//                           workgroup, once base + the rows seen reaches K: a dense mask costs one or two steps.
+// The ranks depend on the mask alone, so the rows are the same for every G.  An item whose `sel` is null selects every
+// doc: docIds 0 .. min(K, num_docs) - 1, no mask read.  No workgroup waits on another; all stores are plain vector stores.
+constexpr int kSelFirstWords = 4;  // mask words per thread and step
+
+struct SelFirstStripe {
+  int64_t c_begin, c_end;  // chunks of kSelFirstWords words
+  int words;
+};
+
+__device__ __forceinline__ SelFirstStripe sel_first_stripe(int num_docs, int G, int wg) {
+  SelFirstStripe s;
+  s.words = num_docs > 0 ? (num_docs + 31) >> 5 : 0;  // the spare word and the bits past num_docs are never used
+  const int64_t chunks = (static_cast<int64_t>(s.words) + kSelFirstWords - 1) / kSelFirstWords;
+  const int64_t per = (chunks + G - 1) / G;
+  s.c_begin = per * wg < chunks ? per * wg : chunks;
+  s.c_end = s.c_begin + per < chunks ? s.c_begin + per : chunks;
+  return s;
+}
+
+// Chunk c of the mask, rows at or past num_docs cleared; all zero at or past c_end.  The 16-byte load is taken only
+// where it ends inside the mask's words + 1 spare word.
+__device__ __forceinline__ uint4 sel_first_chunk(const uint32_t* __restrict__ sel, bool aligned, int64_t c, int64_t c_end,
+                                                 int words, int num_docs) {
+  uint4 m = make_uint4(0u, 0u, 0u, 0u);
+  if (c >= c_end) return m;
+  const int64_t w0 = c * kSelFirstWords;
+  if (aligned && w0 + kSelFirstWords <= static_cast<int64_t>(words) + 1) {
+    m = *reinterpret_cast<const uint4*>(sel + w0);
+  } else {
+    m.x = sel[w0];
+    if (w0 + 1 < words) m.y = sel[w0 + 1];
+    if (w0 + 2 < words) m.z = sel[w0 + 2];
+    if (w0 + 3 < words) m.w = sel[w0 + 3];
+  }
+  const int64_t rem = static_cast<int64_t>(num_docs) - w0 * 32;  // rows of the mask from this chunk on: >= 1
+  if (rem < 32 * kSelFirstWords) {
+    const int r = static_cast<int>(rem);
+    m.x &= r >= 32 ? ~0u : (1u << r) - 1u;
+    m.y &= r >= 64 ? ~0u : (r > 32 ? (1u << (r - 32)) - 1u : 0u);
+    m.z &= r >= 96 ? ~0u : (r > 64 ? (1u << (r - 64)) - 1u : 0u);
+    m.w &= r > 96 ? (1u << (r - 96)) - 1u : 0u;
+  }
+  return m;
+}
+
+__device__ __forceinline__ void sel_first_emit(uint32_t m, int32_t d0, int& rank, int K, int32_t* __restrict__ out) {
+  while (m && rank < K) {
+    out[rank++] = d0 + __builtin_ctz(m);
+    m &= m - 1u;
+  }
+}
+
+// The walk over one stripe, from rank `base` on: returns base + the stripe's selected rows, or some count >= K once
+// that many are known (the same value in every thread).  EMIT: write the docIds of the ranks below K.
+template <bool EMIT>
+__device__ __forceinline__ int sel_first_walk(const uint32_t* __restrict__ sel, const SelFirstStripe& S, int num_docs,
+                                              int base, int K, int32_t* __restrict__ out) {
+  __shared__ int wave_rows[2][kSelBlock / 64];
+  const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(sel) & 15u) == 0;
+  int run = base;
+  int buf = 0;
+  uint4 ahead = sel_first_chunk(sel, aligned, S.c_begin + tid, S.c_end, S.words, num_docs);
+  for (int64_t c0 = S.c_begin; c0 < S.c_end && run < K; c0 += kSelBlock, buf ^= 1) {
+    const int64_t c = c0 + tid;
+    const uint4 m = ahead;
+    ahead = sel_first_chunk(sel, aligned, c + kSelBlock, S.c_end, S.words, num_docs);  // each step loads the next one's
+    const int rows = __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
+    int incl = rows;  // inclusive scan over the wave64
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) wave_rows[buf][wave] = incl;
+    __syncthreads();  // (the buffers alternate: the next step's writes go to the other one)
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kSelBlock / 64; ++w) {
+      const int r = wave_rows[buf][w];
+      before += w < wave ? r : 0;
+      total += r;
+    }
+    if (EMIT) {
+      int rank = run + before + incl - rows;
+      if (rows && rank < K) {
+        const int32_t d0 = static_cast<int32_t>(c * (32 * kSelFirstWords));
+        sel_first_emit(m.x, d0, rank, K, out);
+        sel_first_emit(m.y, d0 + 32, rank, K, out);
+        sel_first_emit(m.z, d0 + 64, rank, K, out);
+        sel_first_emit(m.w, d0 + 96, rank, K, out);
+      }
+    }
+    run += total;
+  }
+  return run;
+}
+
+__global__ void __launch_bounds__(kSelBlock) pgx_select_first_count(const SelItem* __restrict__ items, int nitems, int K,
+                                                                    int32_t* __restrict__ stripe_cnt) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  const int G = static_cast<int>(gridDim.x), wg = static_cast<int>(blockIdx.x);
+  const uint32_t* __restrict__ sel = items[item].sel;
+  const int num_docs = items[item].num_docs;
+  const SelFirstStripe S = sel_first_stripe(num_docs, G, wg);
+  int64_t rows;
+  if (!sel) {  // every doc selected: the stripe's rows
+    const int64_t nd = num_docs > 0 ? num_docs : 0;
+    const int64_t d0 = S.c_begin * (32 * kSelFirstWords), d1 = S.c_end * (32 * kSelFirstWords);
+    rows = (d1 < nd ? d1 : nd) - (d0 < nd ? d0 : nd);
+  } else {
+    rows = sel_first_walk<false>(sel, S, num_docs, 0, K, nullptr);
+  }
+  if (threadIdx.x == 0) stripe_cnt[static_cast<int64_t>(item) * G + wg] = static_cast<int32_t>(rows < K ? rows : K);
+}
+
+// out_lim (may be null): out_lim[item] = min(out_cnt[item], limit), the count the gathers after it run over.
+__global__ void __launch_bounds__(kSelBlock) pgx_select_first(const SelItem* __restrict__ items, int nitems, int K,
+                                                              const int32_t* __restrict__ stripe_cnt,
+                                                              int32_t* __restrict__ out_doc, int32_t* __restrict__ out_cnt,
+                                                              int limit, int32_t* __restrict__ out_lim) {
+  const int item = static_cast<int>(blockIdx.y);
+  if (item >= nitems) return;
+  __shared__ int first_base, first_total;
+  const int G = static_cast<int>(gridDim.x), wg = static_cast<int>(blockIdx.x);
+  const int tid = static_cast<int>(threadIdx.x);
+  const uint32_t* __restrict__ sel = items[item].sel;
+  const int num_docs = items[item].num_docs;
+  int32_t* __restrict__ out = out_doc + static_cast<int64_t>(item) * K;
+  if (!sel) {  // every doc selected
+    if (wg != 0) return;
+    const int n = num_docs < K ? (num_docs > 0 ? num_docs : 0) : K;
+    for (int r = tid; r < n; r += kSelBlock) out[r] = r;
+    if (tid == 0) {
+      out_cnt[item] = n;
+      if (out_lim) out_lim[item] = n < limit ? n : limit;
+    }
+    return;
+  }
+  int base = 0, total = -1;  // total: the item's rows (saturated) when the stripes' counts say it, else from the walk
+  if (G > 1) {
+    if (tid < 64) {  // one lane per stripe: the rows before this workgroup's stripe, and the item's
+      const int v = tid < G ? stripe_cnt[static_cast<int64_t>(item) * G + tid] : 0;
+      int b = tid < wg ? v : 0, t = v;
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) {
+        b += __shfl_xor(b, d, 64);
+        t += __shfl_xor(t, d, 64);
+      }
+      if (tid == 0) {
+        first_base = b;
+        first_total = t;
+      }
+    }
+    __syncthreads();
+    base = first_base;
+    total = first_total;
+    if (base >= K) return;  // the whole workgroup: the K rows lie in earlier stripes (never workgroup 0)
+  }
+  const SelFirstStripe S = sel_first_stripe(num_docs, G, wg);
+  const int run = sel_first_walk<true>(sel, S, num_docs, base, K, out);
+  if (G == 1) total = run;
+  if (wg == 0 && tid == 0) {
+    const int n = total < K ? total : K;
+    out_cnt[item] = n;
+    if (out_lim) out_lim[item] = n < limit ? n : limit;
+  }
+}
+
 }  // namespace pgx
 
 // LDS entries of the candidate buffer for K rows: a power of two (bitonic sort) with room for K kept entries plus one
@@ -512,6 +699,37 @@ extern "C" hipError_t pgx_launch_select_gather(const pgx::SelGatherCol* cols, in
   if (blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pgx::pgx_select_gather, dim3(static_cast<unsigned>(blocks)), dim3(pgx::kSelBlock), 0, stream, cols,
                      nitems, ncols, K, out_doc, out_cnt, out_ids);
+  return hipGetLastError();
+}
+
+// Selection without ORDER BY.  stripe_cnt holds nitems x wgs_per_item counts (item i's stripe g at [i * wgs_per_item +
+// g]); with wgs_per_item > 1 pgx_launch_select_first reads what pgx_launch_select_first_count wrote there on the same
+// stream, with one workgroup per item it reads none (stripe_cnt may be null).  out_doc / out_cnt as the merge writes
+// them: item i's rank r at [i * K + r], ascending docIds, out_cnt[i] = min(matches, K); ranks past the count keep
+// what the caller put there.  out_lim (may be null): nitems counts min(out_cnt[i], limit), 1 <= limit <= K.
+static bool sel_first_args_ok(int nitems, int K, int wgs) {
+  return nitems >= 0 && nitems <= 65535 && K >= 1 && K <= 2048 /* PGX_SEL_MAX_ROWS */ && wgs >= 1 && wgs <= 64;
+}
+
+extern "C" hipError_t pgx_launch_select_first_count(const pgx::SelItem* items, int nitems, int K, int wgs_per_item,
+                                                    int32_t* stripe_cnt, hipStream_t stream) {
+  if (!sel_first_args_ok(nitems, K, wgs_per_item) || !items || !stripe_cnt) return hipErrorInvalidValue;
+  if (nitems == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_select_first_count,
+                     dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)), dim3(pgx::kSelBlock), 0,
+                     stream, items, nitems, K, stripe_cnt);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pgx_launch_select_first(const pgx::SelItem* items, int nitems, int K, int wgs_per_item,
+                                              const int32_t* stripe_cnt, int32_t* out_doc, int32_t* out_cnt, int limit,
+                                              int32_t* out_lim, hipStream_t stream) {
+  if (!sel_first_args_ok(nitems, K, wgs_per_item) || !items || !out_doc || !out_cnt ||
+      (wgs_per_item > 1 && !stripe_cnt) || (out_lim && (limit < 1 || limit > K)))
+    return hipErrorInvalidValue;
+  if (nitems == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgx::pgx_select_first, dim3(static_cast<unsigned>(wgs_per_item), static_cast<unsigned>(nitems)),
+                     dim3(pgx::kSelBlock), 0, stream, items, nitems, K, stripe_cnt, out_doc, out_cnt, limit, out_lim);
   return hipGetLastError();
 }
 

@@ -611,11 +611,21 @@ def select_mv_flag() -> int:
     return N.PGX_Q_SELECT_MV if os.environ.get("PGX_SELECT_MV_NATIVE", "0") == "1" else 0
 
 
+def select_only_flag() -> int:
+    """The flag of a selection query's descriptor: PGX_Q_SELECT_ONLY, with which the library also takes a selection
+    without ORDER BY (MSelectionOnlyOperator: per segment its first `size` docs in docId order, merged by
+    ``merge_selection_rows_unordered``).  The flag is passed only with PGX_SELECT_ONLY_NATIVE=1 (read here, at every
+    request).  Without it such a selection is refused as before the flag: the plan maker's refusal is pinned by
+    tests/test_gpu_select.py, so the route through the plan maker is opt-in, as it is at the ABI."""
+    return N.PGX_Q_SELECT_ONLY if os.environ.get("PGX_SELECT_ONLY_NATIVE", "0") == "1" else 0
+
+
 class _SelectQuery(_Query):
     """A compiled selection query (pgx_select_compile) for one broker request with "selections"."""
 
     def __init__(self, ctx: Context, request: dict, flags: Optional[int] = None):
-        """flags: the descriptor's PGX_Q_* flags; None: what the environment asks for (select_mv_flag)."""
+        """flags: the descriptor's PGX_Q_* flags; None: what the environment asks for (select_mv_flag,
+        select_only_flag)."""
         self.ctx = ctx
         self.request = request
         sel = request["selections"]
@@ -640,7 +650,7 @@ class _SelectQuery(_Query):
             larr[i].column = lkeep[i]
             larr[i].kind = N.PGX_PRED[lf["op"]]
         sd = N.SelectDesc(len(cols), carr, len(self.order_by), oarr, self.offset, self.size, len(nodes), narr,
-                          len(leaves), larr, select_mv_flag() if flags is None else flags)
+                          len(leaves), larr, (select_mv_flag() | select_only_flag()) if flags is None else flags)
         self._keep = [cols, carr, oarr, okeep, narr, larr, lkeep]
         h = C.c_void_p()
         N.check(N.lib().pgx_select_compile(ctx.handle, C.byref(sd), C.byref(h)))
@@ -690,6 +700,16 @@ def merge_selection_rows(lists, types, order_by, limit):
     rows = [r for lst in lists for r in lst]
     rows.sort(key=functools.cmp_to_key(cmp))
     return rows[:limit]
+
+
+def merge_selection_rows_unordered(lists, size):
+    """MCombineOperator's merge of a selection without ORDER BY (CombineService.java:106 ->
+    SelectionOperatorUtils.mergeWithoutOrdering): the segments' (or servers') lists in call order, each list's rows in
+    its own order, up to `size` rows."""
+    rows = []
+    for lst in lists:
+        rows.extend(lst[:max(0, size - len(rows))])
+    return rows
 
 
 def decode_selection(q: _SelectQuery, r, segments: Sequence[IndexSegment]):
@@ -1150,6 +1170,32 @@ class MSelectionOrderByOperator(_GpuOperator):
     nextBlock = next_block
 
 
+class MSelectionOnlyOperator(_GpuOperator):
+    """operator/query/MSelectionOnlyOperator.java over the library's per-segment first rows (docId order); with combine,
+    MCombineOperator's mergeWithoutOrdering: the segments' lists appended in call order up to `size` rows.  The
+    statistics are those of every segment's own early stop, summed (every segment still runs)."""
+
+    def next_block(self):
+        if self._done:
+            return None
+        q = _SelectQuery(self.ctx, self.request)
+        try:
+            r = q.execute(self.segments)
+            try:
+                stats, cols, types, lists = decode_selection(q, r, self.segments)
+            finally:
+                N.lib().pgx_result_release(r)
+        finally:
+            q.close()
+        rows = merge_selection_rows_unordered(lists, q.size)
+        self._stats = stats
+        self._done = True
+        return IntermediateResultsBlock(stats=stats, selection_result=[r[0] for r in rows],
+                                        selection_data_schema=(cols, types), selection_row_ids=[r[1] for r in rows])
+
+    nextBlock = next_block
+
+
 class PlanNode:
     def __init__(self, op_factory):
         self._f = op_factory
@@ -1178,8 +1224,8 @@ class InstancePlanMakerImplV2:
 
     @staticmethod
     def _operator(broker_request: dict):
-        if broker_request.get("selections"):  # ORDER BY or not: the library refuses what it does not run
-            return MSelectionOrderByOperator
+        if broker_request.get("selections"):  # (the library refuses what it does not run)
+            return MSelectionOrderByOperator if broker_request["selections"]["order_by"] else MSelectionOnlyOperator
         return AggregationGroupByOperator if broker_request.get("group_by") else AggregationOperator
 
     def make_inner_segment_plan(self, segment: IndexSegment, broker_request: dict) -> PlanNode:

@@ -40,6 +40,7 @@ PGX_X_THROUGHPUT = 0x8
 PGX_X_SPARSE_GROUP_SETS = 0x10  # the set functions under GROUP BY over sparse / large key spaces (pgx.h)
 PGX_Q_NO_STAR_TREE = 0x1
 PGX_Q_SELECT_MV = 0x2  # pgx_select_desc.flags: the caller reads multi-value columns through pgx_result_select_mv_*
+PGX_Q_SELECT_ONLY = 0x4  # pgx_select_desc.flags: num_order_by == 0 is accepted (MSelectionOnlyOperator)
 ERR_UNSUPPORTED = 2
 PGX_ERR_TIMEOUT = 5
 PGX_ERR_INTERNAL = 6

@@ -15,8 +15,18 @@ Prints one JSON line per case and writes them all to --out.
 segment) to the same shape and times, beside each single-value row, the selection that also returns that column
 (PGX_Q_SELECT_MV): its step, the three pgx_select_mv_* launches, and the bytes that cross to the host.
 
+--no-order-by times the selection without ORDER BY (PGX_Q_SELECT_ONLY, pgx_select_first) on the same segments instead:
+`SELECT f1, f2 FROM T WHERE o2 < 64 LIMIT 10` (one scan leaf: the filter statistic's class b), its ORDER BY o1, o2 DESC
+twin and the same filter as COUNT(*), one step of each in turn, round after round; and the form without a filter on the
+segments and on a second set of an eighth of the rows.  Per query: the median of the steps' wall times (a step ends with
+the result's statistics on the host), their spread (10th and 90th percentile, minimum and maximum) and the kernel time
+per step from the library's timing window.  Then pgx_select_first's kernel time with one workgroup per segment and
+with run_select's own choice (PGX_DEBUG firstg=N, read when the query is compiled), over a mask it leaves early
+(o2 < 64) and one it walks to the end (o1 < 2: fewer matches than the limit), on all segments and on one.
+
   python tools/bench_select.py --out profiles/select/bench_select.json
   python tools/bench_select.py --mv --out profiles/select_mv/bench_select_mv.json
+  python tools/bench_select.py --no-order-by --out profiles/select_only/bench_select_only.json
 """
 import argparse
 import ctypes as C
@@ -50,6 +60,131 @@ def mv_column(name, rows, card=1000, seed=5):
                     np.arange(card).astype(">i4").tobytes(), 4, fwd, None, None, S.DEFAULT_PAD, True, tv, 5)
 
 
+def no_order_by(args):
+    """The --no-order-by mode (module docstring)."""
+    import time
+
+    import numpy as np
+
+    from pinot_amd import engine as E
+    from pinot_amd import native as N
+    from pinot_amd import pql
+    from pinot_amd import synth as S
+
+    cols = [S.ColSpec("f1", 1000, inverted=True), S.ColSpec("f2", 100, inverted=True), S.ColSpec("f3", 10, inverted=True),
+            S.ColSpec("o1", 1 << 20), S.ColSpec("o2", 1 << 10)]
+    wl = S.Workload("sel", "selection without ORDER BY", args.segments, args.rows, cols, "", 9, "weak")
+    ctx = E.Context(0)
+    L = N.lib()
+    flt = " WHERE o2 < 64"
+    results = []
+
+    def compiled(text, firstg=None):
+        """The query for `text`; firstg: workgroups per segment of pgx_select_first (PGX_DEBUG is read at compile)."""
+        old = os.environ.get("PGX_DEBUG")
+        if firstg is not None:
+            os.environ["PGX_DEBUG"] = "firstg=%d" % firstg
+        try:
+            req = pql.compile(text)
+            return E._SelectQuery(ctx, req, flags=N.PGX_Q_SELECT_ONLY) if req.get("selections") else E._Query(ctx, req)
+        finally:
+            if firstg is not None:
+                if old is None:
+                    del os.environ["PGX_DEBUG"]
+                else:
+                    os.environ["PGX_DEBUG"] = old
+
+    def step(q, segs):
+        t0 = time.perf_counter()
+        r = q.execute(segs)
+        st = (C.c_int64 * 4)()
+        N.check(L.pgx_result_stats(r, st))
+        dt = time.perf_counter() - t0
+        L.pgx_result_release(r)
+        return 1e3 * dt, list(st)
+
+    def rounds(queries, segs):
+        """{name: (wall times in ms, one per round, the queries taking turns; statistics; kernel ms per step by name)}"""
+        for _ in range(args.warmup):
+            for q in queries.values():
+                step(q, segs)
+        wall = {name: [] for name in queries}
+        stats = {}
+        for _ in range(args.steps):
+            for name, q in queries.items():
+                ms, stats[name] = step(q, segs)
+                wall[name].append(ms)
+        kern = {}
+        for name, q in queries.items():  # kernel times in a window of their own
+            out = (C.c_double * 3)()
+            js = C.create_string_buffer(1 << 16)
+            N.check(L.pgx_timing_start(ctx.handle))
+            for _ in range(args.steps):
+                step(q, segs)
+            N.check(L.pgx_timing_stop(ctx.handle, out, js, len(js)))
+            detail = json.loads(js.value.decode())
+            detail = detail.get("kernels", detail)
+            kern[name] = (out[0] / args.steps, {k: round(v[1] / args.steps, 5) for k, v in sorted(detail.items())
+                                                if isinstance(v, list) and len(v) == 2})
+        return {name: (wall[name], stats[name], kern[name]) for name in queries}
+
+    def summary(case, name, segs, rows, res):
+        wall, stats, (kernel_ms, per) = res
+        w = np.sort(np.asarray(wall))
+        row = {"case": case, "query": name, "segments": len(segs), "rows_per_segment": rows, "stats": stats,
+               "wall_ms_median": round(float(np.median(w)), 4), "wall_ms_p10": round(float(np.percentile(w, 10)), 4),
+               "wall_ms_p90": round(float(np.percentile(w, 90)), 4), "wall_ms_min": round(float(w[0]), 4),
+               "wall_ms_max": round(float(w[-1]), 4), "kernel_ms_per_step": round(kernel_ms, 4),
+               "kernels_ms_per_step": per, "steps": args.steps, "warmup": args.warmup}
+        results.append(row)
+        print(json.dumps(row), flush=True)
+
+    sets = []
+    for rows in (args.rows, max(1, args.rows // 8)):
+        dev = S.DeviceSegments(ctx, wl, list(range(args.segments)), rows=rows)
+        sets.append((rows, dev))
+    rows, dev = sets[0]
+    segs = dev.segments
+    texts = {"select_only": "SELECT f1, f2 FROM T%s LIMIT 10" % flt,
+             "select_order_by": "SELECT f1, f2 FROM T%s ORDER BY o1, o2 DESC LIMIT 10" % flt,
+             "count": "SELECT COUNT(*) FROM T%s" % flt}
+    queries = {name: compiled(t) for name, t in texts.items()}
+    for name, res in rounds(queries, segs).items():
+        summary("scan_leaf_filter", name, segs, rows, res)
+    for q in queries.values():
+        q.close()
+    # the form without a filter, on both sets: its time must not grow with the segments' rows
+    q = compiled("SELECT f1, f2 FROM T LIMIT 10")
+    for rows_i, dev_i in sets:
+        for name, res in rounds({"select_only": q}, dev_i.segments).items():
+            summary("no_filter", name, dev_i.segments, rows_i, res)
+    q.close()
+    # pgx_select_first alone: one workgroup per segment against run_select's choice
+    for fname, f in (("early_exit", flt), ("walks_whole_mask", " WHERE o1 < 2")):
+        for nseg in (len(segs), 1):
+            for firstg in (1, 0):
+                q = compiled("SELECT f1, f2 FROM T%s LIMIT 10" % f, firstg=firstg)
+                res = rounds({"select_only": q}, segs[:nseg])["select_only"]
+                q.close()
+                per = res[2][1]
+                row = {"case": "first_kernel_" + fname, "segments": nseg, "rows_per_segment": rows,
+                       "workgroups_per_segment": "1" if firstg == 1 else "auto", "docs_found": res[1][0],
+                       "first_ms": per.get("pgx_select_first"), "first_count_ms": per.get("pgx_select_first_count"),
+                       "kernel_ms_per_step": round(res[2][0], 4), "wall_ms_median": round(float(np.median(res[0])), 4),
+                       "steps": args.steps, "warmup": args.warmup}
+                results.append(row)
+                print(json.dumps(row), flush=True)
+    for _, dev_i in sets:
+        dev_i.free()
+    ctx.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"command": " ".join(["python", "tools/bench_select.py"] + sys.argv[1:]), "results": results}, f,
+                      indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segments", type=int, default=64)
@@ -58,7 +193,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--mv", action="store_true", help="also select one multi-value column of about 3 values per doc")
+    ap.add_argument("--no-order-by", action="store_true",
+                    help="time the selection without ORDER BY against its ORDER BY twin and COUNT(*)")
     args = ap.parse_args()
+    if args.no_order_by:
+        return no_order_by(args)
 
     from pinot_amd import engine as E
     from pinot_amd import native as N
